@@ -4,6 +4,7 @@
 metric, config[2] (the single-GPU line uses the same workload at N=1).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config NAME]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...          (one process per GPU, RCCL)
 
 Per-GPU batch 512 by default (round-2 sweep on one MI355X: 11.4k / 12.3k / 12.7k / 12.8k / 13.4k /
@@ -18,9 +19,13 @@ region all-reduced asynchronously on the RCCL stream while the later stages comp
 graph waits for them (distributed.DDPStep; --no-graph launches the same schedule eagerly).
 Timing: barrier + synchronize on both sides of exactly K steps, max over ranks.
 
-Printed on rank 0: ONE JSON line with the metric, a roofline object for the dominant kernel
-(MFMA GEMM of the MLP up-projection, measured here with HIP events on its own stream) and the
-CPU baseline (the fp32 CPU restatement oracle/octo_ref.py, a bounded sample on the host cores).
+Printed on rank 0: ONE JSON line with the metric. A plain run sets up, warms up, times the K
+steps and prints that line (`roofline` and `cpu_baseline` null). --full adds what takes runs of
+its own after the timed steps: a roofline object for the dominant kernel (MFMA GEMM of the MLP
+up-projection, measured here with HIP events on its own stream) with the per-kernel probes, and
+the CPU baseline (the fp32 CPU restatement oracle/octo_ref.py, a bounded sample on the host cores).
+--dump-outputs DIR writes what the last timed step left (loss, parameters, step counter) as
+DIR/<name>.npy (dump_outputs below; --deterministic makes two runs' dumps equal bit for bit).
 """
 from __future__ import annotations
 
@@ -341,6 +346,36 @@ def probe_traffic(B: int):
     return found, src
 
 
+def headline_roofline(model, B, probes):
+    """The `roofline` object of the result line (--full) from the kernel probes: the dominant
+    kernel of the step trace — the weight-gradient GEMM (TN, split-K slabs + combine; ≈ 23 % of
+    kernel time, profiles/r02_b512_kernel_stats_step.csv), at the MLP Dense_0 dW shape — with the
+    committed PMC traffic of every probe; every other probe follows in `kernels`."""
+    cfg = model.cfg
+    traffic, traffic_src = probe_traffic(B)
+    for pr in probes:
+        pr["traffic"] = traffic.get(pr["name"])
+    top = next((p for p in probes if p["name"] == "mlp_dw"), None)
+    sets0, _, _, r0, pr0, _plan0 = model.layer_sets[0]
+    M_ = B * (sum(pr0[1]) if pr0 else sets0.L - r0)
+    N_, K_ = cfg.mlp_dim, cfg.token_embedding_dim
+    if top is None:
+        top = dict(achieved=None, frac=None, traffic=None, kernel="gemm_tn_dma16_kernel",
+                   avg_launch_us=None, flops_per_launch=None)
+    return dict(bound="mfma", achieved=top["achieved"], peak=MFMA_BF16_PEAK_TFLOPS,
+                unit="TFLOP/s", frac=top["frac"], traffic=top["traffic"],
+                kernel=top["kernel"] + " + splitk_epilogue_kernel<1> (MLP Dense_0 weight "
+                "gradient dW += dz1^T . y1: one mmt_gemm launch, split-K GEMM and its combine "
+                "timed together)",
+                shape_MNK=[N_, K_, M_], avg_launch_us=top["avg_launch_us"],
+                flops_per_launch=top["flops_per_launch"],
+                algorithmic_bytes_per_launch=2 * (M_ * N_ + M_ * K_) + 8 * N_ * K_,
+                traffic_source=(f"profiles/{traffic_src} (source digest {source_digest()})"
+                                if traffic_src else "no PMC pass of these kernel sources "
+                                f"(digest {source_digest()}): traffic null"),
+                kernels=[p for p in probes if p is not top])
+
+
 def _cpu_model() -> str:
     try:
         with open("/proc/cpuinfo") as fh:
@@ -418,6 +453,33 @@ def cpu_baseline(cfg_name, model, budget_s=20.0, B=8, max_steps=10):
                        "offline)", other=other)
 
 
+DUMP_SAMPLE_ELEMS = 12_000_000   # 48 MB of fp32, under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, model, state, loss_buf):
+    """What the timed step hands its caller after its last call, as .npy files: loss (float32,
+    the step's diffusion loss), params (float32, the fp32 master parameters after AdamW, the flat
+    buffer in ParamStore order) and step (float64, the train state's device step counter: every
+    step advances it by one, so it reads warmup + steps). The flat gradient is the step's scratch (zeroed at the head of every step)
+    and is not written. A parameter buffer longer than DUMP_SAMPLE_ELEMS is sampled at the sorted
+    indices numpy.sort(default_rng(0).choice(n, DUMP_SAMPLE_ELEMS, replace=False)) — the same
+    indices in every run of the same model, so two dumps compare element for element.
+    The inputs, the initial parameters and every random stream are the same in every run with the
+    same arguments. Without --deterministic the gradients are summed with fp32 atomics, whose
+    order differs from run to run, and training amplifies that (ToMe's matching is discrete): on
+    one MI355X two runs of the same build differ by 4e-10 relative L2 in params after 1 step and
+    by 3e-3 after 25 (loss: equal, then 2 %); with --deterministic the dumps are equal bit for bit."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = model.store.flat.detach().reshape(-1)
+    n = flat.numel()
+    if n > DUMP_SAMPLE_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE_ELEMS, replace=False))
+        flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+    np.save(os.path.join(out_dir, "loss.npy"), loss_buf.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "step.npy"), np.array([state.step], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -429,7 +491,16 @@ def main():
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="config override (A/B runs), e.g. --set fp8=0 on octo-base-hires-tome32")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, parameters and step "
+                         "counter as DIR/<name>.npy (a fixed seeded sample of a long buffer). "
+                         "Inputs are the same in every run; to compare two builds output for "
+                         "output add --deterministic (bit-equal dumps), since the default "
+                         "fp32-atomic gradient sums differ from run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel roofline probes and the "
+                         "CPU baseline (a plain run reports them as null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--overlap-stages", default="auto",
                     help="N > 1: backward stages, each stage's gradient region all-reduced while "
@@ -439,7 +510,7 @@ def main():
                     help="bitwise-reproducible gradients (fixed-point shadow instead of fp32 "
                          "atomics; same as MMT_DETERMINISTIC=1)")
     ap.add_argument("--no-probes", action="store_true",
-                    help="skip the per-kernel roofline probes (rocprofv3 traces of the step alone)")
+                    help="with --full: skip the per-kernel roofline probes")
     ap.add_argument("--probe-only", action="store_true",
                     help="only launch the dominant GEMM (for rocprofv3 --pmc traffic passes)")
     args = ap.parse_args()
@@ -508,41 +579,19 @@ def main():
         elapsed = float(t.item())
     loss_val = float(loss_buf.item())
     K.device_status()  # after the timed region: no device-side index check fired in any step
+    if args.dump_outputs and di.rank == 0:
+        dump_outputs(args.dump_outputs, model, state, loss_buf)
 
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
     if di.rank == 0:
         ms = elapsed / args.steps * 1e3
         value = N * B * args.steps / elapsed
-        probes = [] if args.no_probes else kernel_probes(model, B)
-        traffic, traffic_src = probe_traffic(B)
-        for pr in probes:
-            pr["traffic"] = traffic.get(pr["name"])
-        # headline: the dominant kernel of the step trace — the weight-gradient GEMM (TN, split-K
-        # slabs + combine; ≈ 23 % of kernel time, profiles/r02_b512_kernel_stats_step.csv), at
-        # the MLP Dense_0 dW shape; every other probe follows in `kernels`
-        top = next((p for p in probes if p["name"] == "mlp_dw"), None)
-        sets0, _, _, r0, pr0, _plan0 = model.layer_sets[0]
-        M_ = B * (sum(pr0[1]) if pr0 else sets0.L - r0)
-        N_, K_ = cfg.mlp_dim, cfg.token_embedding_dim
-        if top is None:
-            top = dict(achieved=None, frac=None, traffic=None, kernel="gemm_tn_dma16_kernel",
-                       avg_launch_us=None, flops_per_launch=None)
-        roof = dict(bound="mfma", achieved=top["achieved"], peak=MFMA_BF16_PEAK_TFLOPS,
-                    unit="TFLOP/s", frac=top["frac"], traffic=top["traffic"],
-                    kernel=top["kernel"] + " + splitk_epilogue_kernel<1> (MLP Dense_0 weight "
-                    "gradient dW += dz1^T . y1: one mmt_gemm launch, split-K GEMM and its combine "
-                    "timed together)",
-                    shape_MNK=[N_, K_, M_], avg_launch_us=top["avg_launch_us"],
-                    flops_per_launch=top["flops_per_launch"],
-                    algorithmic_bytes_per_launch=2 * (M_ * N_ + M_ * K_) + 8 * N_ * K_,
-                    traffic_source=(f"profiles/{traffic_src} (source digest {source_digest()})"
-                                    if traffic_src else "no PMC pass of these kernel sources "
-                                    f"(digest {source_digest()}): traffic null"),
-                    kernels=[p for p in probes if p is not top])
         fps = algorithmic_flops_per_sample(model)
-        cpu = None
-        if N == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args.config, model, budget_s=args.cpu_budget)
+        roof = cpu = None
+        if args.full:
+            roof = headline_roofline(model, B, [] if args.no_probes else kernel_probes(model, B))
+            if N == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(args.config, model, budget_s=args.cpu_budget)
         sets0 = model.layer_sets[0][0]
         line = {
             "metric": "train samples/sec OCTO-small 256px+text, ToMe r=16, 1/2/4/8 MI355X",

@@ -27,7 +27,7 @@ for step in "$@"; do
     golden) timeout -k 10 240 $T -s tests/test_golden_step_gpu.py ;;
     gpu_all) timeout -k 10 900 $T -m gpu tests ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) timeout -k 10 600 python -u bench.py ;;
+    bench) timeout -k 10 600 python -u bench.py --full ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac > "gpurun_out/$step.log" 2>&1
   rc=$?

@@ -1,16 +1,19 @@
 """Headline roofline agreement: the bench line's HIP-event time of the headline probe (MLP Dense_0
 dW: split-K TN GEMM + combine, one mmt_gemm launch) against rocprofv3's kernel trace of the same
 command (the probe launches after the last AdamW of the trace).
-usage: headline_agreement.py TAG  (reads gpurun_out/TAG_benchprof/**/run_kernel_trace.csv and
-profiles/TAG_bench.json; prints the profiles/TAG_headline_agreement.txt text)"""
+usage: headline_agreement.py TAG  (reads $OUT/TAG_benchprof/**/run_kernel_trace.csv, the trace
+tools/gpu_measure.sh wrote of `bench.py --full`, OUT default bench_out, and profiles/TAG_bench.json;
+prints the profiles/TAG_headline_agreement.txt text)"""
 import csv
 import glob
 import json
+import os
 import statistics
 import sys
 
 tag = sys.argv[1]
-tr = glob.glob(f"gpurun_out/{tag}_benchprof/**/run_kernel_trace.csv", recursive=True)[0]
+out = os.environ.get("OUT", "bench_out")
+tr = glob.glob(f"{out}/{tag}_benchprof/**/run_kernel_trace.csv", recursive=True)[0]
 rows = sorted(csv.DictReader(open(tr)), key=lambda r: int(r["Start_Timestamp"]))
 last = max(i for i, r in enumerate(rows) if "adamw_kernel" in r["Kernel_Name"])
 after = rows[last + 1:]
