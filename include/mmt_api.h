@@ -80,8 +80,9 @@ int mmt_det_flush(float* grad, long long* fx, int64_t n, mmt_stream_t stream);
 /* Bytes of caller-provided device workspace an entry point needs (the library
  * allocates nothing; scratch comes from the caller). op / dims:
  *   MMT_WS_TOME_MATCH  {n, t, c}  (mmt_tome_match)
+ *   MMT_WS_GRAD_NORM   {n}        (mmt_optim_prepare)
  * Returns the byte count, or a negative MMT_ERR_* code. */
-enum { MMT_WS_TOME_MATCH = 1 };
+enum { MMT_WS_TOME_MATCH = 1, MMT_WS_GRAD_NORM = 2 };
 int64_t mmt_workspace_size(int op, const int64_t* dims, int ndims);
 
 /* ------------------------------------------------------------------ ToMe
@@ -551,6 +552,64 @@ int mmt_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, i
               float grad_scale, mmt_stream_t stream);
 int mmt_cast_f32_bf16(const float* a, void* b, int64_t n, mmt_stream_t stream);
 int mmt_step_advance(int32_t* state, mmt_stream_t stream);
+
+/* Device-resident optimizer control: the learning rate of a schedule, the global gradient norm
+ * and the clip factor are computed on the device and read by AdamW from device memory, so one
+ * captured graph serves a whole run (optax.chain(clip_by_global_norm(max_norm),
+ * adamw(schedule)); the reference takes any optax tx from its caller, octo.py:341,377).
+ *
+ * Schedules of s = state[1] (the count BEFORE this step's advance, as optax scale_by_schedule),
+ * W = warmup_steps, T = decay_steps, evaluated in double and rounded to fp32 once:
+ *   CONSTANT       peak_value
+ *   WARMUP_COSINE  optax.warmup_cosine_decay_schedule: s < W: init + (peak - init) s / W; else
+ *                  c = min(s - W, T - W), a = end / peak:
+ *                  peak ((1 - a) (1 + cos(pi c / (T - W))) / 2 + a)
+ *   WARMUP_RSQRT   the same warm-up; s >= W: peak sqrt(timescale / (s - W + timescale))
+ *
+ * opt: 8 caller-owned fp32 words on the device, written by mmt_optim_prepare:
+ *   0 grad_norm  grad_scale * sqrt(sum g^2): the norm of the averaged gradient before clipping
+ *   1 clip       max_norm > 0: 1 if grad_norm < max_norm else max_norm / grad_norm
+ *                (optax.clip_by_global_norm, no epsilon); max_norm <= 0: always 1
+ *   2 gmul       grad_scale * clip, formed in double, rounded once: the only factor the update
+ *                applies to g[i]
+ *   3 lr         schedule(state[1])
+ *   4 nonfinite  1 if sum g^2 is not finite, else 0
+ *   5 skipped    running count of skipped steps (accumulated; every other word is overwritten)
+ *   6 skip       nonfinite && skip_nonfinite
+ *   7 0
+ *
+ * mmt_optim_prepare is two launches, no atomics, no host sync, graph-capturable:
+ *   1. MMT_GRAD_NORM_GRID workgroups of 256 lanes (a constant: not a function of the device);
+ *      workgroup b owns the 16-B vectors [b * per, (b + 1) * per) of g, per = ceil((n / 4) /
+ *      MMT_GRAD_NORM_GRID), clipped to n / 4; the n % 4 tail elements go to the last workgroup.
+ *      Every workgroup stores one fp32 partial (0 for an empty chunk) into workspace, which
+ *      need not be zeroed.
+ *   2. one workgroup adds the partials in double in a fixed order and writes opt.
+ * The partition and both trees are fixed, so opt is bitwise reproducible from run to run.
+ * Longest chain of fp32 roundings on any path to sum g^2 (each g^2 enters by one fused
+ * multiply-add): ceil(per / 1024) + 1 (tail) + 4 (a lane's 16 accumulators) + 6 (wave64
+ * tree) + 2 (4 waves) = ceil(per / 1024) + 13; 24 at 90 M elements.
+ * g: 16-B aligned. workspace: >= mmt_workspace_size(MMT_WS_GRAD_NORM, {n}) bytes. sched is read
+ * on the host at launch.
+ *
+ * mmt_adamw_dev is mmt_adamw with lr = opt[3] and grad_scale = opt[2] (the same update
+ * function: bit-identical to mmt_adamw given the same fp32 values); when opt[6] != 0 it
+ * returns at once and p, m, v and the shadow are not touched. */
+enum { MMT_SCHED_CONSTANT = 0, MMT_SCHED_WARMUP_COSINE = 1, MMT_SCHED_WARMUP_RSQRT = 2 };
+typedef struct {            /* zero-initialise, then set; read on the host at launch */
+  int kind;
+  double init_value, peak_value, end_value;   /* CONSTANT uses peak_value */
+  int64_t warmup_steps, decay_steps;          /* decay_steps: COSINE only (total, warm-up included) */
+  double timescale;                           /* RSQRT only */
+} mmt_lr_schedule_t;
+#define MMT_GRAD_NORM_GRID 2048
+
+int mmt_optim_prepare(const float* g, int64_t n, float grad_scale, double max_norm,
+                      int skip_nonfinite, const mmt_lr_schedule_t* sched, const int32_t* state,
+                      float* opt, void* workspace, int64_t ws_bytes, mmt_stream_t stream);
+int mmt_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n,
+                  const int32_t* state, const float* opt, double b1, double b2, double eps,
+                  double wd, mmt_stream_t stream);
 
 #ifdef __cplusplus
 }

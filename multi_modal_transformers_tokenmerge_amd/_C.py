@@ -92,6 +92,8 @@ SIGNATURES: dict[str, list] = {
     "mmt_cast_f32_bf16": [P, P, L, P],
     "mmt_transpose_bf16_batched": [P, P, P, I, L, P],
     "mmt_step_advance": [P, P],
+    "mmt_optim_prepare": [P, L, F, D, I, P, P, P, P, L, P],
+    "mmt_adamw_dev": [P, P, P, P, P, L, P, P, D, D, D, D, P],
 }
 _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)
@@ -159,7 +161,12 @@ def exported_symbols() -> list[str]:
     return ["mmt_last_error", *SIGNATURES.keys()]
 
 
-WS_TOME_MATCH = 1  # mmt_workspace_size op codes (include/mmt_api.h)
+WS_TOME_MATCH, WS_GRAD_NORM = 1, 2  # mmt_workspace_size op codes (include/mmt_api.h)
+# MMT_GRAD_NORM_GRID: workgroups of mmt_optim_prepare's partial-sum launch (GRAD_NORM_GRID * 256
+# lanes * 4 elements = one full 16-B pass of the grid); OPT_WORDS: the fp32 words of `opt`
+GRAD_NORM_GRID = 2048
+OPT_WORDS = 8
+OPT_GRAD_NORM, OPT_CLIP, OPT_GMUL, OPT_LR, OPT_NONFINITE, OPT_SKIPPED, OPT_SKIP = range(7)
 
 
 def workspace_size(op: int, *dims: int) -> int:

@@ -5,3 +5,5 @@ Mirrors the module/config API of the reference ``multi_modal_transformers`` pack
 in the hand-written HIP library ``libmmt_hip.so`` (C ABI: include/mmt_api.h).
 """
 __version__ = "0.1.0"
+
+from .schedules import Constant, WarmupCosine, WarmupRsqrt  # noqa: E402,F401

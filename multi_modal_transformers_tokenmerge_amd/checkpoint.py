@@ -15,7 +15,7 @@
   dict, e.g. a local t5-base) into the frozen T5 store (the reference's text encoder is
   ``FlaxT5EncoderModel(AutoConfig.from_pretrained('t5-base'))``, t5_base.py:11).
 * ``save_train_state`` / ``load_train_state``: resume files (flat fp32 master, AdamW moments, RNG
-  state) via ``torch.save`` of plain tensors, loaded with ``weights_only=True``.
+  state, the optimizer's device-side words when it keeps any) via ``torch.save`` of plain tensors, loaded with ``weights_only=True``.
 
 Parity: no checkpoint of the reference exists anywhere (its orbax dependency is unused,
 pyproject.toml:33-34), so the tree layout is restated from the Flax module definitions and is
@@ -383,9 +383,14 @@ def hf_t5_to_store(t5, state_dict: Dict[str, torch.Tensor]) -> None:
 # ---------------------------------------------------------------- resume files
 def save_train_state(path: str, train_state) -> None:
     s = train_state.model.store
-    torch.save({"flat": s.flat.cpu(), "m": s.m.cpu(), "v": s.v.cpu(),
-                "rng": train_state.rng.cpu(), "sample_offset": torch.tensor(train_state.sample_offset),
-                "names": [p.name for p in s.params], "n": torch.tensor(s.n)}, path)
+    d = {"flat": s.flat.cpu(), "m": s.m.cpu(), "v": s.v.cpu(),
+         "rng": train_state.rng.cpu(), "sample_offset": torch.tensor(train_state.sample_offset),
+         "names": [p.name for p in s.params], "n": torch.tensor(s.n)}
+    if getattr(train_state, "opt", None) is not None:
+        # device-side optimizer words (the skipped-step count; the rest is rewritten every
+        # step). The schedule itself needs nothing saved: it is a function of rng[1].
+        d["opt"] = train_state.opt.cpu()
+    torch.save(d, path)
 
 
 def load_train_state(path: str, train_state) -> None:
@@ -398,4 +403,9 @@ def load_train_state(path: str, train_state) -> None:
     s.v.copy_(d["v"].to(s.v.device))
     train_state.rng.copy_(d["rng"].to(train_state.rng.device))
     train_state.sample_offset = int(d["sample_offset"])
+    if getattr(train_state, "opt", None) is not None:
+        if "opt" in d:
+            train_state.opt.copy_(d["opt"].to(train_state.opt.device))
+        else:  # a file written before the optimizer kept device-side words
+            train_state.opt.zero_()
     s.sync_shadow()

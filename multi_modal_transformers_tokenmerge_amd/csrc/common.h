@@ -19,6 +19,10 @@ void set_error(const char* fmt, ...);
 
 // workspace sizes (bytes) behind mmt_workspace_size
 int64_t tome_match_workspace(int64_t n, int64_t t, int64_t c);
+// mmt_optim_prepare: one fp32 partial per workgroup of its fixed grid, whatever n is
+inline int64_t grad_norm_workspace(int64_t /*n*/) {
+  return (int64_t)MMT_GRAD_NORM_GRID * (int64_t)sizeof(float);
+}
 
 #define MMT_CHECK_ARG(cond, ...)              \
   do {                                        \

@@ -73,6 +73,12 @@ extern "C" int64_t mmt_workspace_size(int op, const int64_t* dims, int ndims) {
         return MMT_ERR_INVALID;
       }
       return mmt::tome_match_workspace(dims[0], dims[1], dims[2]);
+    case MMT_WS_GRAD_NORM:
+      if (!dims || ndims != 1 || dims[0] <= 0) {
+        mmt::set_error("mmt_workspace_size(GRAD_NORM): dims must be {n}");
+        return MMT_ERR_INVALID;
+      }
+      return mmt::grad_norm_workspace(dims[0]);
     default:
       mmt::set_error("mmt_workspace_size: unknown op %d", op);
       return MMT_ERR_INVALID;

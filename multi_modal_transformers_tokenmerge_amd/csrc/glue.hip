@@ -528,11 +528,15 @@ __global__ void embedding_gather_kernel(const int32_t* __restrict__ ids, int64_t
 
 // AdamW (optax.adamw semantics, decoupled weight decay on every parameter, bias-corrected
 // moments) over the flat fp32 master buffer; writes the bf16 shadow used by the GEMMs.
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                             float* __restrict__ m, float* __restrict__ v,
-                             bf16_t* __restrict__ shadow, int64_t n, const int32_t* __restrict__ state,
-                             float lr, double b1d, double b2d, float eps, float wd, float grad_scale) {
-  const int step = state[1] + 1;
+// One update function for both kernels below, so their arithmetic is the same instructions.
+// The grid-stride bounds come from the kernels: blockDim / gridDim read inside a kernel body
+// fold to the uniform-workgroup form, read in a device function they do not.
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g,
+                                             float* __restrict__ m, float* __restrict__ v,
+                                             bf16_t* __restrict__ shadow, int64_t n,
+                                             const int step, float lr,
+                                             double b1d, double b2d, float eps, float wd,
+                                             float grad_scale, int64_t first, int64_t stride) {
   // the betas arrive in double (optax / torch hold them as Python floats): 1 - b and the bias
   // corrections are formed in double and rounded once (fp32 1.f - 0.999f would differ from
   // (float)0.001 by 1.3e-5 relative)
@@ -540,8 +544,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   const float bc1 = (float)(1.0 - pow(b1d, (double)step));
   const float bc2 = (float)(1.0 - pow(b2d, (double)step));
   const float omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < n; i += stride) {
     const float gi = g[i] * grad_scale;
     const float mi = b1 * m[i] + omb1 * gi;
     const float vi = b2 * v[i] + omb2 * (gi * gi);
@@ -552,6 +555,137 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     p[i] = pn;
     if (shadow) shadow[i] = f2bf(pn);
   }
+}
+
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                             float* __restrict__ m, float* __restrict__ v,
+                             bf16_t* __restrict__ shadow, int64_t n, const int32_t* __restrict__ state,
+                             float lr, double b1d, double b2d, float eps, float wd, float grad_scale) {
+  adamw_update(p, g, m, v, shadow, n, state[1] + 1, lr, b1d, b2d, eps, wd, grad_scale,
+               (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// AdamW with the learning rate, the gradient factor and the skip flag read from the device
+// words mmt_optim_prepare wrote (include/mmt_api.h: opt[3], opt[2], opt[6]). The skip test is
+// uniform over the grid. The four device scalars are loaded side by side before it (the empty
+// asm pins them there): tested first, opt[6] is one more dependent scalar load from memory in
+// front of every wave, ahead of the one for state[1].
+__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                 float* __restrict__ m, float* __restrict__ v,
+                                 bf16_t* __restrict__ shadow, int64_t n,
+                                 const int32_t* __restrict__ state, const float* __restrict__ opt,
+                                 double b1d, double b2d, float eps, float wd) {
+  const float skip = opt[6], lr = opt[3], gmul = opt[2];
+  const int step = state[1] + 1;
+  asm volatile("" ::"s"(skip), "s"(lr), "s"(gmul), "s"(step));
+  if (skip != 0.f) return;
+  adamw_update(p, g, m, v, shadow, n, step, lr, b1d, b2d, eps, wd, gmul,
+               (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// Sum of squares of the flat gradient, launch 1 of mmt_optim_prepare: GN_GRID workgroups (a
+// constant, so the partition depends on n alone), workgroup b owns the 16-B vectors
+// [b * per, (b + 1) * per) clipped to n / 4, per = ceil((n / 4) / GN_GRID); the n % 4 tail
+// elements go to the last workgroup. A lane keeps 4 independent 16-B loads in flight, each with
+// its own 4 accumulators (one fused multiply-add per element), then fixed trees: the lane's 16
+// accumulators (4 levels), the wave's 64 lanes by xor shuffles (6), the 4 waves through LDS (2).
+// Longest chain of fp32 roundings on any path: ceil(per / 1024) + 1 (tail) + 4 + 6 + 2.
+// No atomics; every workgroup stores its partial, an empty chunk stores 0.
+constexpr int GN_GRID = MMT_GRAD_NORM_GRID;
+
+__device__ __forceinline__ void sumsq_acc(float4& a, const float4 x) {
+  a.x = fmaf(x.x, x.x, a.x);
+  a.y = fmaf(x.y, x.y, a.y);
+  a.z = fmaf(x.z, x.z, a.z);
+  a.w = fmaf(x.w, x.w, a.w);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n,
+                                                         float* __restrict__ partial) {
+  __shared__ float wsum[4];
+  const int64_t n4 = n >> 2;
+  const int64_t per = (n4 + GN_GRID - 1) / GN_GRID;
+  const int64_t lo = std::min<int64_t>((int64_t)blockIdx.x * per, n4);
+  const int64_t hi = std::min<int64_t>(lo + per, n4);
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+  int64_t i = lo + threadIdx.x;
+  for (; i + 768 < hi; i += 1024) {
+    const float4 x0 = g4[i], x1 = g4[i + 256], x2 = g4[i + 512], x3 = g4[i + 768];
+    sumsq_acc(a0, x0);
+    sumsq_acc(a1, x1);
+    sumsq_acc(a2, x2);
+    sumsq_acc(a3, x3);
+  }
+  if (i < hi) sumsq_acc(a0, g4[i]);
+  if (i + 256 < hi) sumsq_acc(a1, g4[i + 256]);
+  if (i + 512 < hi) sumsq_acc(a2, g4[i + 512]);
+  if (blockIdx.x == GN_GRID - 1 && (int64_t)threadIdx.x < (n & 3)) {
+    const float t = g[4 * n4 + threadIdx.x];
+    a0.x = fmaf(t, t, a0.x);
+  }
+  const float sx = (a0.x + a1.x) + (a2.x + a3.x), sy = (a0.y + a1.y) + (a2.y + a3.y);
+  const float sz = (a0.z + a1.z) + (a2.z + a3.z), sw = (a0.w + a1.w) + (a2.w + a3.w);
+  float s = (sx + sy) + (sz + sw);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+struct OptimCtl {
+  mmt_lr_schedule_t sched;
+  double grad_scale, max_norm;
+  int skip_nonfinite;
+};
+
+__device__ double lr_schedule(const mmt_lr_schedule_t& sc, int64_t s) {
+  if (sc.kind == MMT_SCHED_CONSTANT) return sc.peak_value;
+  const int64_t W = sc.warmup_steps;
+  if (s < W) return sc.init_value + (sc.peak_value - sc.init_value) * (double)s / (double)W;
+  if (sc.kind == MMT_SCHED_WARMUP_COSINE) {
+    const int64_t span = sc.decay_steps - W;
+    const double c = (double)std::min<int64_t>(s - W, span);
+    const double alpha = sc.end_value / sc.peak_value;
+    const double cosine = 0.5 * (1.0 + cos(3.141592653589793 * c / (double)span));
+    return sc.peak_value * ((1.0 - alpha) * cosine + alpha);
+  }
+  return sc.peak_value * sqrt(sc.timescale / ((double)(s - W) + sc.timescale));
+}
+
+// Launch 2 of mmt_optim_prepare: one workgroup adds the GN_GRID partials in double in a fixed
+// order (a lane's GN_GRID / 256 partials in sequence, then a halving tree through LDS) and lane
+// 0 writes the 8 opt words (include/mmt_api.h).
+__global__ __launch_bounds__(256) void optim_finalise_kernel(const float* __restrict__ partial,
+                                                             const int32_t* __restrict__ state,
+                                                             float* __restrict__ opt,
+                                                             const OptimCtl ctl) {
+  __shared__ double red[256];
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < GN_GRID / 256; ++j) acc += (double)partial[threadIdx.x + 256 * j];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double sumsq = red[0];
+  const bool nonfinite = !isfinite(sumsq);
+  const double norm = ctl.grad_scale * sqrt(sumsq);
+  double clip = 1.0;
+  if (ctl.max_norm > 0.0 && !(norm < ctl.max_norm)) clip = ctl.max_norm / norm;
+  const bool skip = nonfinite && ctl.skip_nonfinite;
+  opt[0] = (float)norm;
+  opt[1] = (float)clip;
+  opt[2] = (float)(ctl.grad_scale * clip);
+  opt[3] = (float)lr_schedule(ctl.sched, (int64_t)state[1]);
+  opt[4] = nonfinite ? 1.f : 0.f;
+  opt[5] += skip ? 1.f : 0.f;
+  opt[6] = skip ? 1.f : 0.f;
+  opt[7] = 0.f;
 }
 
 // Transposed bf16 weight shadows: dst (cols, rows) = src (rows, cols)^T for a batch of matrices
@@ -834,6 +968,55 @@ extern "C" int mmt_adamw(float* p, const float* g, float* m, float* v, void* sha
                      (bf16_t*)shadow_bf16, n, state, (float)lr, b1, b2, (float)eps, (float)wd,
                      grad_scale);
   MMT_CHECK_LAUNCH("mmt_adamw");
+  return MMT_OK;
+}
+
+extern "C" int mmt_optim_prepare(const float* g, int64_t n, float grad_scale, double max_norm,
+                                 int skip_nonfinite, const mmt_lr_schedule_t* sched,
+                                 const int32_t* state, float* opt, void* workspace,
+                                 int64_t ws_bytes, mmt_stream_t stream) {
+  MMT_CHECK_ARG(g && sched && state && opt && workspace, "mmt_optim_prepare: null argument");
+  MMT_CHECK_ARG(n > 0, "mmt_optim_prepare: n = %lld", (long long)n);
+  MMT_CHECK_ARG((reinterpret_cast<uintptr_t>(g) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(workspace) & 3) == 0,
+                "mmt_optim_prepare: g must be 16-B aligned (workspace 4-B)");
+  MMT_CHECK_ARG(ws_bytes >= mmt::grad_norm_workspace(n),
+                "mmt_optim_prepare: workspace %lld B < %lld B (mmt_workspace_size)",
+                (long long)ws_bytes, (long long)mmt::grad_norm_workspace(n));
+  const mmt_lr_schedule_t& sc = *sched;
+  MMT_CHECK_ARG(sc.kind == MMT_SCHED_CONSTANT || sc.kind == MMT_SCHED_WARMUP_COSINE ||
+                    sc.kind == MMT_SCHED_WARMUP_RSQRT,
+                "mmt_optim_prepare: unknown schedule kind %d", sc.kind);
+  if (sc.kind != MMT_SCHED_CONSTANT)
+    MMT_CHECK_ARG(sc.warmup_steps >= 1, "mmt_optim_prepare: warmup_steps %lld < 1",
+                  (long long)sc.warmup_steps);
+  if (sc.kind == MMT_SCHED_WARMUP_COSINE) {
+    MMT_CHECK_ARG(sc.peak_value != 0.0, "mmt_optim_prepare: cosine peak_value 0 (alpha = end / peak)");
+    MMT_CHECK_ARG(sc.decay_steps > sc.warmup_steps,
+                  "mmt_optim_prepare: cosine decay_steps %lld <= warmup_steps %lld",
+                  (long long)sc.decay_steps, (long long)sc.warmup_steps);
+  }
+  if (sc.kind == MMT_SCHED_WARMUP_RSQRT)
+    MMT_CHECK_ARG(sc.timescale > 0.0, "mmt_optim_prepare: rsqrt timescale %g <= 0", sc.timescale);
+  float* partial = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GN_GRID), dim3(256), 0, as_stream(stream), g, n,
+                     partial);
+  MMT_CHECK_LAUNCH("mmt_optim_prepare (partial sums)");
+  const OptimCtl ctl{sc, (double)grad_scale, max_norm, skip_nonfinite != 0};
+  hipLaunchKernelGGL(optim_finalise_kernel, dim3(1), dim3(256), 0, as_stream(stream),
+                     (const float*)partial, state, opt, ctl);
+  MMT_CHECK_LAUNCH("mmt_optim_prepare (finalise)");
+  return MMT_OK;
+}
+
+extern "C" int mmt_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow_bf16,
+                             int64_t n, const int32_t* state, const float* opt, double b1,
+                             double b2, double eps, double wd, mmt_stream_t stream) {
+  MMT_CHECK_ARG(p && g && m && v && state && opt && n > 0, "mmt_adamw_dev: args");
+  const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 8);
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), p, g, m, v,
+                     (bf16_t*)shadow_bf16, n, state, opt, b1, b2, (float)eps, (float)wd);
+  MMT_CHECK_LAUNCH("mmt_adamw_dev");
   return MMT_OK;
 }
 

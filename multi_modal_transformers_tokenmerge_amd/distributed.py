@@ -239,6 +239,8 @@ class DDPStep:
         snap = [t.clone() for t in (st.flat, st.flat_bf16, st.m, st.v, s.rng)]
         if s.metrics is not None:
             snap += [s.metrics.total.clone(), s.metrics.count.clone()]
+        if s.opt is not None:  # device-side optimizer words (the skipped-step count accumulates)
+            snap.append(s.opt.clone())
         return snap
 
     def _restore(self, snap):
@@ -246,6 +248,8 @@ class DDPStep:
         dst = [st.flat, st.flat_bf16, st.m, st.v, s.rng]
         if s.metrics is not None:
             dst += [s.metrics.total, s.metrics.count]
+        if s.opt is not None:
+            dst.append(s.opt)
         for d, v in zip(dst, snap):
             d.copy_(v)
         st.refresh_transposed()

@@ -11,16 +11,19 @@ MI355X design of the step (SURVEY §3.1 call stack):
                 table evaluated inside the attention kernel, never an (B, H, L, L) tensor
   backbone    : StackedEncoder1DBlock with ToMe, explicit fwd/bwd (attention_blocks/attention.py)
   head        : diffusion denoise loss (action_heads/diffusion.py)
-  optimizer   : one fused AdamW launch over the flat parameter buffer; device step counter
+  optimizer   : one fused AdamW launch over the flat parameter buffer; device step counter;
+                optionally a learning-rate schedule, global-norm clipping and non-finite-step
+                skipping evaluated on the device (AdamW, OCTOTrainState.opt)
 Everything after the input upload is stream-ordered device work with no host sync, so the whole
 step is captured into a HIP graph and replayed (see OCTOTrainState.graphed_step).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Union
 
 import numpy as np
 import torch
@@ -33,6 +36,7 @@ from ...action_heads.diffusion import DiffusionActionHead
 from ...attention_blocks.attention import LayerCtx, StackedEncoder1DBlock
 from ...layers import Dense, wgrad_overlap
 from ...params import ParamStore, he_normal, normal
+from ...schedules import Constant, Schedule, WarmupCosine, WarmupRsqrt
 from ...tokenizers.images.image_tokenizer import ImageTokenizer
 from ...tokenizers.readout.readout import AddPositionEmbedding
 from ...tokenizers.text.t5_base import T5Tokenizer
@@ -459,12 +463,40 @@ class Octo:
 @dataclass
 class AdamW:
     """The reference takes an optax tx from its caller (octo.py:341); this is optax.adamw with
-    these defaults (decoupled weight decay applied to every parameter, as optax without a mask)."""
-    learning_rate: float = 3e-4
+    these defaults (decoupled weight decay applied to every parameter, as optax without a mask).
+
+    learning_rate: a float, or a schedule (schedules.Constant / WarmupCosine / WarmupRsqrt)
+    evaluated on the device from the step counter. max_grad_norm: optax.clip_by_global_norm
+    chained in front (None: off). skip_nonfinite: a step whose gradient has a non-finite norm
+    leaves the parameters and both moments untouched. With a float learning rate and neither
+    option the step is the plain mmt_adamw launch; otherwise the learning rate, the gradient norm
+    and the clip factor live in device memory (OCTOTrainState.opt), so one captured graph serves
+    the whole schedule."""
+    learning_rate: Union[float, Constant, WarmupCosine, WarmupRsqrt] = 3e-4
     b1: float = 0.9
     b2: float = 0.999
     eps: float = 1e-8
     weight_decay: float = 1e-4
+    max_grad_norm: Optional[float] = None
+    skip_nonfinite: bool = False
+
+    def __post_init__(self):
+        if not isinstance(self.learning_rate, (int, float) + Schedule):
+            raise TypeError(f"AdamW: learning_rate {self.learning_rate!r} is neither a number nor "
+                            "a schedules.Constant / WarmupCosine / WarmupRsqrt")
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0:
+            raise ValueError(f"AdamW: max_grad_norm {self.max_grad_norm} must be > 0 (None: off)")
+
+    @property
+    def device_control(self) -> bool:
+        """The optimizer's scalars are computed on the device (mmt_optim_prepare)."""
+        return (not isinstance(self.learning_rate, (int, float))
+                or self.max_grad_norm is not None or self.skip_nonfinite)
+
+    @property
+    def schedule(self):
+        lr = self.learning_rate
+        return Constant(float(lr)) if isinstance(lr, (int, float)) else lr
 
 
 class OCTOMetrics:
@@ -502,6 +534,19 @@ class OCTOTrainState:
     sample_offset: int = 0
     metrics: Optional[OCTOMetrics] = None
     last_loss: Optional[torch.Tensor] = None    # loss of the latest step (device)
+    # device-resident optimizer control (tx.device_control): the 8 fp32 words mmt_optim_prepare
+    # writes (include/mmt_api.h: grad_norm, clip, gmul, lr, nonfinite, skipped, skip, 0) for
+    # loggers that must not synchronise, and its workspace; None for the plain optimizer
+    opt: Optional[torch.Tensor] = None
+    opt_workspace: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        if self.tx.device_control and self.opt is None:
+            dev, n = self.model.device, self.model.store.flat.numel()
+            self.opt = torch.zeros(_C.OPT_WORDS, dtype=torch.float32, device=dev)
+            self.opt_workspace = torch.empty(_C.workspace_size(_C.WS_GRAD_NORM, n),
+                                             dtype=torch.uint8, device=dev)
+        self._sched_c = self.tx.schedule.to_c() if self.tx.device_control else None
 
     @property
     def params(self):
@@ -511,6 +556,30 @@ class OCTOTrainState:
     def step(self) -> int:
         return int(self.rng[1].item())
 
+    def _opt_word(self, i: int) -> float:
+        if self.opt is None:
+            raise AttributeError("the optimizer keeps no device-side state (plain AdamW: float "
+                                 "learning rate, no clipping, no skip)")
+        return float(self.opt[i].item())
+
+    # host reads of `opt` (each synchronises with the device): the latest step's values
+    @property
+    def last_grad_norm(self) -> float:
+        """Global norm of the averaged gradient before clipping."""
+        return self._opt_word(_C.OPT_GRAD_NORM)
+
+    @property
+    def last_lr(self) -> float:
+        return self._opt_word(_C.OPT_LR)
+
+    @property
+    def last_clip(self) -> float:
+        return self._opt_word(_C.OPT_CLIP)
+
+    @property
+    def skipped_steps(self) -> int:
+        return int(self._opt_word(_C.OPT_SKIPPED))
+
     def apply_gradients(self):
         with phase("optimizer"):
             self._apply_gradients()
@@ -518,10 +587,24 @@ class OCTOTrainState:
     def _apply_gradients(self):
         s = self.model.store
         tx = self.tx
-        _C.call("mmt_adamw", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m), _C.ptr(s.v),
-                _C.ptr(s.flat_bf16), s.flat.numel(), _C.ptr(self.rng), tx.learning_rate, tx.b1,
-                tx.b2, tx.eps, tx.weight_decay, getattr(self.allreduce, "grad_scale", 1.0),
-                _C.stream_ptr())
+        grad_scale = getattr(self.allreduce, "grad_scale", 1.0)
+        if self.opt is None:
+            _C.call("mmt_adamw", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m), _C.ptr(s.v),
+                    _C.ptr(s.flat_bf16), s.flat.numel(), _C.ptr(self.rng), tx.learning_rate, tx.b1,
+                    tx.b2, tx.eps, tx.weight_decay, grad_scale, _C.stream_ptr())
+        else:
+            # after the all-reduce, so every rank reduces the same summed gradient to the same
+            # bits. A skipped step (skip_nonfinite) still refreshes the shadows (a no-op on
+            # unchanged weights) and advances the counter, which keys the random streams: unlike
+            # optax.apply_if_finite, the bias-correction count includes skipped steps.
+            n = s.flat.numel()
+            _C.call("mmt_optim_prepare", _C.ptr(s.flat_grad), n, grad_scale,
+                    float(tx.max_grad_norm or 0.0), int(tx.skip_nonfinite),
+                    ctypes.addressof(self._sched_c), _C.ptr(self.rng), _C.ptr(self.opt),
+                    _C.ptr(self.opt_workspace), self.opt_workspace.numel(), _C.stream_ptr())
+            _C.call("mmt_adamw_dev", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
+                    _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt),
+                    tx.b1, tx.b2, tx.eps, tx.weight_decay, _C.stream_ptr())
         s.refresh_transposed()
         s.refresh_fp8()
         _C.call("mmt_step_advance", _C.ptr(self.rng), _C.stream_ptr())
