@@ -322,6 +322,37 @@ int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H,
                  float keep_prob, const void* o, int64_t o_s_b, int64_t o_s_t, const void* dout,
                  int64_t d_s_b, int64_t d_s_t, const float* lse, float* delta, void* dqkv,
                  int64_t dq_s_b, int64_t dq_s_t, float* bias_grad, mmt_stream_t stream);
+/* The same two with a per-sample, per-key additive logit shared by all heads and queries (ToMe
+ * proportional attention, key_bias[b, k] = log size[b, k]: a merged token votes as the patches it
+ * stands for):  logits[b,h,q,k] = scale * q.k + key_bias[b,k], then mask, softmax and dropout as
+ * above. key_bias == NULL is mmt_attn_fwd / mmt_attn_bwd (which forward here with NULL).
+ * key_bias: fp32, row b at key_bias + b*kb_s_b; kb_s_b a multiple of 4 and >= roundup(L, 64); the
+ * base 16-B aligned. Entries [0, L) are used and must be finite; entries [L, roundup(L, 64)) must
+ * be readable and are ignored (the kernels load aligned float4s, so L needs no multiple of 4).
+ * lse includes the bias and the backward recomputes P with it; no gradient with respect to
+ * key_bias is produced (sizes come from the non-differentiable match). Rejected
+ * (MMT_ERR_INVALID, nothing launched): key_bias with wsum, and key_bias with the T5 `bias`.
+ * With key_bias the Dh 64, 32 < L <= 320 backward always takes the two-phase resident kernel. */
+int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H, int Dh,
+                         float scale, int n_sets, const int32_t* set_start, const int32_t* set_len,
+                         const uint32_t* set_vis, const uint32_t* drop_bits, float keep_prob,
+                         const float* bias, void* o, int64_t o_s_b, int64_t o_s_t, float* lse,
+                         float* wsum, const float* key_bias, int64_t kb_s_b, mmt_stream_t stream);
+int mmt_attn_bwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H, int Dh,
+                         float scale, int n_sets, const int32_t* set_start, const int32_t* set_len,
+                         const uint32_t* set_vis, const uint32_t* drop_bits,
+                         const uint32_t* drop_bits_t, float keep_prob, const void* o, int64_t o_s_b,
+                         int64_t o_s_t, const void* dout, int64_t d_s_b, int64_t d_s_t,
+                         const float* lse, float* delta, void* dqkv, int64_t dq_s_b, int64_t dq_s_t,
+                         float* bias_grad, const float* key_bias, int64_t kb_s_b,
+                         mmt_stream_t stream);
+/* The key_bias rows of a ToMe layer from its token sizes: kb[b, set_start + j] = logf(size[b, j])
+ * for j < t (size: fp32 (B, t) contiguous, > 0; kb rows of kb_s_b floats, L <= kb_s_b). With
+ * zero_rest != 0 it also writes 0 over the rest of [0, roundup(L, 64)) (tokens of unmerged sets,
+ * and the padding), so one merged set is one launch with no memset; several merged sets are one
+ * launch each, the first with zero_rest. */
+int mmt_tome_size_bias(const float* size, int B, int t, int set_start, int L, float* kb,
+                       int64_t kb_s_b, int zero_rest, mmt_stream_t stream);
 /* Keep mask of a dropout stream (flax Dropout keep-mask, broadcast over batch and heads for
  * attention): keep(r, c) iff keep_elem(key(rng, layer, site), r*cols + c), i.e. the 16-bit half
  * (idx & 1) of mix32(key ^ (idx >> 1)) is below floor(keep_prob * 65536).

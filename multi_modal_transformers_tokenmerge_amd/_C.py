@@ -59,6 +59,10 @@ SIGNATURES: dict[str, list] = {
     "mmt_im2col_same": [P, L, I, I, I, I, P, P],
     "mmt_col2im_same": [P, L, I, I, I, I, P, P],
     "mmt_attn_bwd": [P, L, L, I, I, I, I, F, I, P, P, P, P, P, F, P, L, L, P, L, L, P, P, P, L, L, P, P],
+    "mmt_attn_fwd_keybias": [P, L, L, I, I, I, I, F, I, P, P, P, P, F, P, P, L, L, P, P, P, L, P],
+    "mmt_attn_bwd_keybias": [P, L, L, I, I, I, I, F, I, P, P, P, P, P, F, P, L, L, P, L, L, P, P, P,
+                             L, L, P, P, L, P],
+    "mmt_tome_size_bias": [P, I, I, I, I, P, L, I, P],
     "mmt_dropout_bits": [P, U32, U32, I, I, F, P, P, P],
     "mmt_seqnorm_fwd": [P, I, L, L, I, I, I, P, P, F, P, L, L, P, P, P],
     "mmt_seqnorm_bwd": [P, I, L, L, P, I, L, L, I, I, I, P, P, P, P, L, L, P, L, L, P, P, P],

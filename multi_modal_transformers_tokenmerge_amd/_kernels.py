@@ -434,13 +434,32 @@ def attn_bwd_resident(L: int, Dh: int) -> bool:
     return os.environ.get("MMT_ATTN_RES_BWD", "1") != "0" and Dh == 64 and 32 < L <= 320
 
 
+def _check_key_bias(key_bias: torch.Tensor, B: int, L: int):
+    """key_bias: fp32 (B, >= L) rows with unit inner stride. The row stride rule (a multiple of 4,
+    >= attn_lp(L): the kernels load aligned float4s up to the padded length) is the library's check."""
+    if (key_bias.dim() != 2 or key_bias.dtype != torch.float32 or key_bias.shape[0] != B
+            or key_bias.shape[1] < L or key_bias.stride(1) != 1):
+        raise ValueError(f"key_bias must be fp32 (B={B}, >= L={L}) with unit inner stride "
+                         "(K.tome_size_bias builds it)")
+    # a stride the library accepts makes it read attn_lp(L) floats of every row: the last row's
+    # must lie inside the tensor's storage (a narrow view of a wider buffer is fine)
+    lp, sb = attn_lp(L), key_bias.stride(0)
+    if sb >= lp and key_bias.shape[1] < lp:
+        have = key_bias.untyped_storage().nbytes() // 4 - key_bias.storage_offset()
+        if (B - 1) * sb + lp > have:
+            raise ValueError(f"key_bias rows must be readable up to attn_lp(L) = {lp} floats")
+
+
 def attn_fwd(qkv: torch.Tensor, H: int, scale: float, table: SetTable | None = None,
              drop_bits: torch.Tensor | None = None, keep_prob: float = 1.0,
              bias: torch.Tensor | None = None, out: torch.Tensor | None = None,
-             wsum: torch.Tensor | None = None):
+             wsum: torch.Tensor | None = None, key_bias: torch.Tensor | None = None):
     """wsum (optional fp32 (B, H, L)): receives the per-query sum of the post-dropout attention
-    weights (the pruning importance, compressed_attention.py:302-306)."""
-    _dev(qkv, drop_bits, bias, out, wsum)
+    weights (the pruning importance, compressed_attention.py:302-306).
+    key_bias (optional fp32 (B, attn_lp(L)) rows): an additive logit per (sample, key) shared by
+    heads and queries — ToMe proportional attention's log token size (tome_size_bias); entries past
+    L are ignored. Not with wsum or bias (include/mmt_api.h mmt_attn_fwd_keybias)."""
+    _dev(qkv, drop_bits, bias, out, wsum, key_bias)
     B, L, Dh = _qkv_geo(qkv, H)
     t = table or SetTable.none(L)
     if t.L != L:
@@ -456,9 +475,14 @@ def attn_fwd(qkv: torch.Tensor, H: int, scale: float, table: SetTable | None = N
     if wsum is not None and (tuple(wsum.shape) != (B, H, L) or wsum.dtype != torch.float32
                              or not wsum.is_contiguous()):
         raise ValueError("wsum must be contiguous fp32 (B, H, L)")
-    _C.call("mmt_attn_fwd", ptr(qkv), qkv.stride(0), qkv.stride(1), B, L, H, Dh, scale, t.n,
-            t.starts, t.lens, t.vis, ptr(drop_bits), keep_prob, ptr(bias), ptr(out), out.stride(0),
-            out.stride(1), ptr(lse), ptr(wsum), _C.stream_ptr())
+    args = (ptr(qkv), qkv.stride(0), qkv.stride(1), B, L, H, Dh, scale, t.n, t.starts, t.lens,
+            t.vis, ptr(drop_bits), keep_prob, ptr(bias), ptr(out), out.stride(0), out.stride(1),
+            ptr(lse), ptr(wsum))
+    if key_bias is None:
+        _C.call("mmt_attn_fwd", *args, _C.stream_ptr())
+    else:
+        _check_key_bias(key_bias, B, L)
+        _C.call("mmt_attn_fwd_keybias", *args, ptr(key_bias), key_bias.stride(0), _C.stream_ptr())
     return out, lse
 
 
@@ -469,9 +493,10 @@ def attn_lp(L: int) -> int:
 
 def attn_bwd(qkv, o, dout, lse, H: int, scale: float, table: SetTable | None = None,
              drop_bits=None, keep_prob: float = 1.0, dqkv: torch.Tensor | None = None,
-             bias_grad: torch.Tensor | None = None):
-    """bias_grad (fp32 [3*H*Dh], optional) += column sums of dqkv (the QKV bias gradient)."""
-    _dev(qkv, o, dout, lse, drop_bits, dqkv, bias_grad)
+             bias_grad: torch.Tensor | None = None, key_bias: torch.Tensor | None = None):
+    """bias_grad (fp32 [3*H*Dh], optional) += column sums of dqkv (the QKV bias gradient).
+    key_bias: the forward's (lse includes it; it gets no gradient)."""
+    _dev(qkv, o, dout, lse, drop_bits, dqkv, bias_grad, key_bias)
     B, L, Dh = _qkv_geo(qkv, H)
     t = table or SetTable.none(L)
     if dout.stride(-1) != 1 or o.stride(-1) != 1:
@@ -486,11 +511,37 @@ def attn_bwd(qkv, o, dout, lse, H: int, scale: float, table: SetTable | None = N
     if bias_grad is not None and (bias_grad.dtype != torch.float32 or bias_grad.numel() != 3 * H * Dh
                                   or not bias_grad.is_contiguous()):
         raise ValueError("bias_grad must be contiguous fp32 [3*H*Dh]")
-    _C.call("mmt_attn_bwd", ptr(qkv), qkv.stride(0), qkv.stride(1), B, L, H, Dh, scale, t.n,
-            t.starts, t.lens, t.vis, ptr(bits), ptr(bits_t), keep_prob, ptr(o), o.stride(0), o.stride(1),
-            ptr(dout), dout.stride(0), dout.stride(1), ptr(lse), ptr(delta), ptr(dqkv),
-            dqkv.stride(0), dqkv.stride(1), ptr(bias_grad), _C.stream_ptr())
+    args = (ptr(qkv), qkv.stride(0), qkv.stride(1), B, L, H, Dh, scale, t.n, t.starts, t.lens,
+            t.vis, ptr(bits), ptr(bits_t), keep_prob, ptr(o), o.stride(0), o.stride(1), ptr(dout),
+            dout.stride(0), dout.stride(1), ptr(lse), ptr(delta), ptr(dqkv), dqkv.stride(0),
+            dqkv.stride(1), ptr(bias_grad))
+    if key_bias is None:
+        _C.call("mmt_attn_bwd", *args, _C.stream_ptr())
+    else:
+        _check_key_bias(key_bias, B, L)
+        _C.call("mmt_attn_bwd_keybias", *args, ptr(key_bias), key_bias.stride(0), _C.stream_ptr())
     return dqkv
+
+
+def tome_size_bias(B: int, L: int, sets, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Proportional attention's key bias of a ToMe layer: fp32 (B, attn_lp(L)) with
+    log(size[b, j]) at set_start + j for each (set_start, t, size) of `sets` (size: fp32 (B, t), the
+    token sizes a merge handed on) and 0 for the tokens of every other set and the padding.
+    One launch per set, no memset (the first launch also zeroes the rest)."""
+    sets = list(sets)
+    if not sets:
+        raise ValueError("tome_size_bias needs at least one (set_start, t, size)")
+    _dev(*[s[2] for s in sets], out)
+    if out is None:
+        out = torch.empty((B, attn_lp(L)), dtype=torch.float32, device=sets[0][2].device)
+    elif (tuple(out.shape) != (B, attn_lp(L)) or out.dtype != torch.float32 or out.stride(1) != 1):
+        raise ValueError(f"out must be fp32 (B, attn_lp(L)) = {(B, attn_lp(L))}")
+    for i, (start, t, size) in enumerate(sets):
+        if tuple(size.shape) != (B, t) or size.dtype != torch.float32 or not size.is_contiguous():
+            raise ValueError(f"size must be contiguous fp32 (B, t) = {(B, t)}, got {tuple(size.shape)}")
+        _C.call("mmt_tome_size_bias", ptr(size), B, t, start, L, ptr(out), out.stride(0),
+                1 if i == 0 else 0, _C.stream_ptr())
+    return out
 
 
 # ------------------------------------------------------------------------ seq LayerNorm etc.

@@ -10,7 +10,10 @@ Semantics kept from the reference:
     mask broadcast over batch and heads; q/k/v/out DenseGeneral with bias (fused QKV here);
   * MLPBlock: Dense -> relu -> Dropout -> Dense -> Dropout (the YAML key ``norm`` is the Dropout);
   * ToMe metric = sum over heads of the key projection of the image token set, merged with
-    merge_wavg and the set's token sizes carried across layers (no proportional attention);
+    merge_wavg and the set's token sizes carried across layers; with LayerCtx.prop_attn
+    (OctoConfig.proportional_attention) the sizes also enter the next blocks' softmax as the
+    ToMe paper's proportional attention, softmax(q.k * scale + log size[k]), a per-key bias
+    inside the attention kernels (the reference stops short of it, tome_attention.py:251);
   * top-k pruning (OctoConfig.compression == "prune"): importance = mean over keys, then over
     heads, of the post-dropout attention weights (compressed_attention.py:302-306, written by the
     attention forward as per-query row sums), compute_top_k_tokens per token set
@@ -55,12 +58,37 @@ class LayerCtx:
     tome_forced: Optional[tuple] = None  # injected (unm, src, dst) in place of the matching (tests;
     #                                      a list of triples, one per merged set, with several)
     tome_plan: tuple = ()          # ((set index, r), ...): one ToMe match + merge per compressed set
+    prop_attn: bool = False        # proportional attention: + log(size) on the keys of merged sets
+    size_set: int = -1             # set of the incoming single-tensor `size` when this block merges
+    #                                none itself (else: the block's merged set)
 
     def tome_sets(self):
         """The merged sets as ((set index, r), ...)."""
         if self.tome_plan:
             return tuple(self.tome_plan)
         return ((self.tome_set, self.r),) if self.r > 0 else ()
+
+    def sized_sets(self, size):
+        """The incoming token sizes as [(set_start, t, size (B, t)), ...]: `size` is the tensor of
+        the one merged set or the per-set dict of several (Encoder1DBlock.forward)."""
+        if isinstance(size, dict):
+            items = sorted(size.items())
+        else:
+            plan = self.tome_sets()
+            si = plan[0][0] if len(plan) == 1 else self.size_set
+            if si < 0:
+                raise ValueError("proportional attention: the set of the incoming token sizes is "
+                                 "unknown (LayerCtx.size_set)")
+            items = [(si, size)]
+        out = []
+        for si, sz in items:
+            if sz is None:
+                continue
+            s0, t = self.sets.starts[si], self.sets.lens[si]
+            if sz.shape[1] != t:
+                raise ValueError(f"token sizes of set {si}: {sz.shape[1]} entries for {t} tokens")
+            out.append((s0, t, sz))
+        return out
 
 
 _SIDE = {}
@@ -307,7 +335,14 @@ class Encoder1DBlock(Bindable):
             bits = K.dropout_bits(ctx.rng, ctx.layer, DROP_ATTN, L, L, kpa)
         wsum = (torch.empty((B, H, L), dtype=torch.float32, device=x.device)
                 if ctx.prune is not None else None)
-        o, lse = K.attn_fwd(qkv, H, self.scale, ctx.table, bits, kpa, wsum=wsum)
+        kbias = None
+        if ctx.prop_attn and size is not None:
+            # proportional attention: log(size) on the keys of the merged sets, 0 on the others
+            # (one small launch per merged set on the main stream; block 0 has no sizes yet)
+            sized = ctx.sized_sets(size)
+            if sized:
+                kbias = K.tome_size_bias(B, L, sized)
+        o, lse = K.attn_fwd(qkv, H, self.scale, ctx.table, bits, kpa, wsum=wsum, key_bias=kbias)
         prune = None
         o_in, x_res, Lo = o, x, L
         if ctx.prune is not None:
@@ -364,7 +399,7 @@ class Encoder1DBlock(Bindable):
                                     **drop(DROP_MLP_OUT, L2, kpm))
         saved = dict(x=x, y0=y0, mu0=mu0, rs0=rs0, qkv=qkv, o=o, o_in=o_in, lse=lse, bits=bits,
                      x1=x1, y1=y1, mu1=mu1, rs1=rs1, h=h, hbits=hbits, tome=tome, prune=prune,
-                     kp=kp, kpm=kpm, kpa=kpa,
+                     kp=kp, kpm=kpm, kpa=kpa, kbias=kbias,
                      # every merge of the block in the order applied (one set: [tome]; several:
                      # the last set first, `tome` then None)
                      tome_sets=tome_sets)
@@ -425,7 +460,8 @@ class Encoder1DBlock(Bindable):
             dx1 = K.topk_scatter_bwd(dx1.view(B, Lo, D), pidx, L)
         # the QKV bias gradient (column sums of dqkv) is accumulated inside the attention backward
         dqkv = K.attn_bwd(sv["qkv"], sv["o"], do.view(B, L, D), sv["lse"], self.H, self.scale,
-                          ctx.table, sv["bits"], kpa, bias_grad=self.qkv.b.grad)
+                          ctx.table, sv["bits"], kpa, bias_grad=self.qkv.b.grad,
+                          key_bias=sv.get("kbias"))
         dy0 = self.qkv.bwd(dqkv.view(B * L, 3 * D), sv["y0"].view(B * L, D), bias_grad_done=True)
         if prev is not None and sv["x"].dtype == torch.float32 and dy0.dtype == torch.bfloat16:
             pblk, psv, pctx = prev

@@ -333,6 +333,46 @@ __device__ __forceinline__ void store_rows_lds(const floatx16* acc, float sc, bf
   __builtin_amdgcn_wave_barrier();  // the region may be rewritten next
 }
 
+// ------------------------------------------------------------ key bias (proportional attention)
+// An optional additive logit per (sample, key), shared by heads and queries (ToMe's log token
+// size): logits = scale q.k + key_bias[b, k]. It is a column constant of the score tile, so in
+// the forward kernels and the tiled dQ it enters as the INITIAL QK^T accumulator in pre-scale
+// units (key_bias / scale): the running max, the exact-max pass, the lazy rescale and the masking
+// (which overwrites it with -inf) see biased scores and need no change. The resident backward
+// and dK/dV, which have no running max, add it in the exponent (with the row's -lse) instead.
+// Rows are fp32, 16-B aligned and padded to lp_of(L) readable floats,
+// so the aligned float4 of a register group is in bounds for any L; the padding only ever lands in
+// masked scores. Template flag KB: the KB = false instantiations are the code without it.
+// Queries on the lanes: registers 4 j .. 4 j + 3 of a 32-key tile are keys 8 j + 4 hh + {0..3}.
+__device__ __forceinline__ floatx16 kb_load(const float* kb_tile, int hh) {
+  floatx16 a;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float4 x = *reinterpret_cast<const float4*>(kb_tile + 8 * j + 4 * hh);
+    a[4 * j] = x.x; a[4 * j + 1] = x.y; a[4 * j + 2] = x.z; a[4 * j + 3] = x.w;
+  }
+  return a;
+}
+// The initial score accumulator of a 32-key tile: zeros, or the tile's key bias / scale.
+template <bool KB>
+__device__ __forceinline__ floatx16 kb_init(const float* kb_tile, float inv_scale, int hh) {
+  floatx16 a;
+  if constexpr (KB) {
+    a = kb_load(kb_tile, hh);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] *= inv_scale;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+  }
+  return a;
+}
+// Keys on the lanes (dK / dV): one scalar per lane, in log2 units (0 for a key past L).
+__device__ __forceinline__ float kb_lane(const float* kb_row, int key, int L) {
+  const float v = kb_row[min(key, L - 1)];
+  return key < L ? v * LOG2E : 0.f;
+}
+
 // =============================================================================== forward
 // One workgroup = 4 waves over 128 NQ query rows of one (sample, head): wave w owns the NQ
 // 32-row query blocks w, w + 4, ..., each with its own Q fragments, O^T accumulators and
@@ -340,11 +380,12 @@ __device__ __forceinline__ void store_rows_lds(const floatx16* acc, float sc, bf
 // workgroup covers L <= 256 rows, so K and V of a (sample, head) are read from HBM once and each
 // LDS tile feeds NQ x 16 MFMAs per wave instead of 16, which amortises the per-tile barrier and
 // the per-workgroup prologue (the launch picks NQ per L, mmt_attn_fwd).
-template <int DH, int NQ, bool WS, bool DROP, int NW = 4>
+template <int DH, int NQ, bool WS, bool DROP, int NW = 4, bool KB = false>
 __global__ __launch_bounds__(64 * NW, DH > 128 ? 1 : 2) void attn_fwd_kernel(
     Geo g, AttnMask mask, const uint32_t* __restrict__ drop_q, int drop_lp, float drop_scale,
     const float* __restrict__ bias, bf16_t* __restrict__ o, int64_t o_s_b, int64_t o_s_t,
-    float* __restrict__ lse, float* __restrict__ wsum) {
+    float* __restrict__ lse, float* __restrict__ wsum, const float* __restrict__ key_bias,
+    int64_t kb_s_b) {
   constexpr int STR = DH + 8;
   constexpr int NS = DH / 16;   // k-steps over the head dim
   constexpr int ND = DH / 32;   // 32-row d sub-tiles of O^T
@@ -428,8 +469,9 @@ __global__ __launch_bounds__(64 * NW, DH > 128 ? 1 : 2) void attn_fwd_kernel(
           for (int r = 0; r < 16; ++r) sacc[u][r] = -INFINITY;
           continue;
         }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sacc[u][r] = 0.f;
+        // the scores start from the sub-tile's key bias / scale (KB) or 0
+        sacc[u] = kb_init<KB>(KB ? key_bias + (int64_t)b * kb_s_b + kt + 32 * u : nullptr,
+                              1.f / g.scale, hh);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
           sacc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<STR>(Ks, 32 * u, s, lane),
@@ -644,11 +686,11 @@ __device__ __forceinline__ bf16x8 res_trans_at(const char* img_rows, const int (
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int NTILE, bool DROP, bool WS, bool ONEPASS>
+template <int NTILE, bool DROP, bool WS, bool ONEPASS, bool KB = false>
 __global__ __launch_bounds__(64 * RES_NW, 2) void attn_fwd_res_kernel(
     Geo g, AttnMask mask, ResPlan plan, const uint32_t* __restrict__ drop_q, int drop_lp,
     float drop_scale, bf16_t* __restrict__ o, int64_t o_s_b, int64_t o_s_t, float* __restrict__ lse,
-    float* __restrict__ wsum) {
+    float* __restrict__ wsum, const float* __restrict__ key_bias, int64_t kb_s_b) {
   constexpr int DH = 64, NS = 4, ROWS = 32 * NTILE;
   __shared__ __attribute__((aligned(16))) bf16_t smem[2 * ROWS * DH];  // [K | V] images
   const int bh = blockIdx.x, b = bh / g.H, h = bh - b * g.H;
@@ -674,6 +716,10 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_fwd_res_kernel(
     }
   }
   const float c2 = g.scale * LOG2E;
+  // the sample's key-bias row, read from global memory per tile (cache-resident: every head and
+  // query block of the sample reads the same <= 1.25 KB; the two workgroups of a CU leave no LDS)
+  const float* kbl = KB ? key_bias + (int64_t)b * kb_s_b : nullptr;
+  const float inv_scale = 1.f / g.scale;
   // per-lane LDS byte offsets of the K row fragments (row lr of a tile, chunk 2s + hh)
   const int swr = res_sw(lr);
   int koff[NS];
@@ -778,14 +824,16 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_fwd_res_kernel(
     // tile t + 1 and the K fragments of tile t + 2 are issued before the softmax of tile t, and
     // tile t's V^T fragments before it, so MFMA / LDS latencies hide under the VALU work
     bf16x8 kr[NS];
+    floatx16 kbr;  // KB: the tile's key bias, fetched with its K fragments (one stage ahead of qk)
     auto kread = [&](int t) {
 #pragma unroll
       for (int s = 0; s < NS; ++s) kr[s] = *reinterpret_cast<const bf16x8*>(smc + t * 4096 + koff[s]);
+      if constexpr (KB) kbr = kb_load(kbl + 32 * t, hh);
     };
     auto qk = [&]() {
       floatx16 acc;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[r] = KB ? kbr[r] * inv_scale : 0.f;
 #pragma unroll
       for (int s = 0; s < NS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[s], qf[s], acc, 0, 0, 0);
       return acc;
@@ -1071,13 +1119,14 @@ __device__ __forceinline__ void res_store_rows(const floatx16 (&acc)[2], float s
     }
 }
 
-template <int NTILE, bool DROP>
+template <int NTILE, bool DROP, bool KB = false>
 __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
     Geo g, AttnMask mask, ResPlanB plan, const uint32_t* __restrict__ drop_q,
     const uint32_t* __restrict__ drop_k, int drop_lp, float drop_scale,
     const bf16_t* __restrict__ dout, int64_t d_s_b, int64_t d_s_t, const float* __restrict__ lse,
     const bf16_t* __restrict__ o, int64_t o_s_b, int64_t o_s_t, float* __restrict__ rc,
-    bf16_t* __restrict__ dqkv, int64_t dq_s_b, int64_t dq_s_t, float* __restrict__ bias_grad) {
+    bf16_t* __restrict__ dqkv, int64_t dq_s_b, int64_t dq_s_t, float* __restrict__ bias_grad,
+    const float* __restrict__ key_bias, int64_t kb_s_b) {
   constexpr int DH = 64, NS = 4, ROWS = 32 * NTILE, LP = ROWS;
   constexpr int IMG_BYTES = 2 * ROWS * DH * 2, RED_BYTES = RES_NW * 64 * 16 * 4;
   __shared__ __attribute__((aligned(16))) char smem_raw[IMG_BYTES > RED_BYTES ? IMG_BYTES : RED_BYTES];
@@ -1092,6 +1141,8 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
   float* rc1 = rc0 + LP;
   const float c2 = g.scale * LOG2E;
   const float kp = 1.f / drop_scale;
+  // the sample's key-bias row (read from global memory: as the resident forward)
+  const float* kbl = KB ? key_bias + (int64_t)b * kb_s_b : nullptr;
   const char* img0 = smem_raw;
   const char* img1 = img0 + ROWS * DH * 2;
   int koff[NS];  // row-fragment offsets (row lr of a 32-row tile, chunk 2 s + hh)
@@ -1184,6 +1235,11 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
 #endif
         TileMasks<16> dm;
         if constexpr (DROP) dm.load(drop_q, drop_lp, blk, 32 * t);
+        // KB: the tile's key bias, loaded here (inside the tile's branch: fetched tile by tile,
+        // not all up front, which spilled) and used after the MFMAs, in the exponent below: no
+        // running max in the backward, so it need not sit in the accumulator
+        floatx16 kbt;
+        if constexpr (KB) kbt = kb_load(kbl + 32 * t, hh);
         floatx16 sacc, pacc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1208,7 +1264,7 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
         floatx16 ds;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = fast_exp2(fmaf(sacc[r], c2, -lse2));
+          const float p = fast_exp2(fmaf(sacc[r], c2, KB ? fmaf(kbt[r], LOG2E, -lse2) : -lse2));
           float tt = pacc[r];
           if constexpr (DROP) tt = sel_keep(tt, dm.m[r]);
           ds[r] = p * (tt - dkp);
@@ -1266,6 +1322,7 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
     const bool kv = key < L;
     const int kc = kv ? key : L - 1;
     const int nblk = slot + 1 < RES_SLOTS ? plan.kblk[wave][slot + 1] : 0xff;
+    const float kb2 = KB ? kb_lane(kbl, key, L) : 0.f;  // this lane's key bias, log2 units
     const int sk = set_of(mask, kc);
     const int sk0 = __builtin_amdgcn_readfirstlane(sk);
     const bool uni = mask.causal == 0u && __all(sk == sk0);
@@ -1330,7 +1387,8 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
         floatx16 pk, ds;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = fast_exp2(sacc[r] * c2);
+          // (the key's bias, a lane constant here, rides in the conversion to log2 units)
+          const float p = fast_exp2(KB ? fmaf(sacc[r], c2, kb2) : sacc[r] * c2);
           if constexpr (DROP) {
             const bool keep = __builtin_amdgcn_inverse_ballot_w64(dm.m[r]);
             pk[r] = keep ? p : 0.f;
@@ -1833,7 +1891,7 @@ static void res8_items(const AttnMask& m, int L, ResPlanB& pb) {
 }
 
 // =============================================================================== bwd: dQ
-template <int DH, int NTT, bool DROP>
+template <int DH, int NTT, bool DROP, bool KB = false>
 __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dq_kernel(Geo g, AttnMask mask,
                                                          const uint32_t* __restrict__ drop_q,
                                                          int drop_lp, float drop_scale,
@@ -1845,7 +1903,9 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dq_kernel(Geo 
                                                          float* __restrict__ delta,
                                                          bf16_t* __restrict__ dqkv,
                                                          int64_t dq_s_b, int64_t dq_s_t,
-                                                         float* __restrict__ bgrad) {
+                                                         float* __restrict__ bgrad,
+                                                         const float* __restrict__ key_bias,
+                                                         int64_t kb_s_b) {
   constexpr int STR = DH + 8;
   constexpr int NS = DH / 16;
   constexpr int ND = DH / 32;
@@ -1923,12 +1983,12 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dq_kernel(Geo 
       for (int u = 0; u < 2; ++u) {
         TileMasks<16> dm;  // dropout lane masks of (query word, key sub-tile): scalar loads
         if constexpr (DROP) dm.load(drop_q, drop_lp, (q0 >> 5) + wave, kt + 32 * u);
-        floatx16 sacc, pacc;
+        // the scores start from the sub-tile's key bias / scale (KB), as in the forward
+        floatx16 sacc = kb_init<KB>(KB ? key_bias + (int64_t)b * kb_s_b + kt + 32 * u : nullptr,
+                                    1.f / g.scale, hh);
+        floatx16 pacc;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sacc[r] = 0.f;
-          pacc[r] = 0.f;
-        }
+        for (int r = 0; r < 16; ++r) pacc[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<STR>(Ks, 32 * u, s, lane), qf[s],
@@ -1992,7 +2052,7 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dq_kernel(Geo 
 }
 
 // =============================================================================== bwd: dK, dV
-template <int DH, int NTT, bool DROP>
+template <int DH, int NTT, bool DROP, bool KB = false>
 __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dkdv_kernel(Geo g, AttnMask mask,
                                                            const uint32_t* __restrict__ drop_k,
                                                            int drop_lp, float drop_scale,
@@ -2002,7 +2062,9 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dkdv_kernel(Ge
                                                            const float* __restrict__ delta,
                                                            bf16_t* __restrict__ dqkv,
                                                            int64_t dq_s_b, int64_t dq_s_t,
-                                                           float* __restrict__ bgrad) {
+                                                           float* __restrict__ bgrad,
+                                                           const float* __restrict__ key_bias,
+                                                           int64_t kb_s_b) {
   constexpr int STR = DH + 8;
   constexpr int NS = DH / 16;
   constexpr int ND = DH / 32;
@@ -2039,6 +2101,8 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dkdv_kernel(Ge
     for (int i = 0; i < mask.n_sets; ++i) selq |= ((mask.vis[i] >> sk) & 1u) << i;
   const int64_t row_bh = ((int64_t)b * g.H + h) * L;
   const float sl2 = g.scale * LOG2E;
+  // this lane's key bias in log2 units: it joins the row's -lse in the score conversion
+  const float kb2 = KB ? kb_lane(key_bias + (int64_t)b * kb_s_b, key, L) : 0.f;
   floatx16 dk[ND], dv[ND];
 #pragma unroll
   for (int d = 0; d < ND; ++d)
@@ -2113,7 +2177,8 @@ __global__ __launch_bounds__(NTT, DH > 128 ? 1 : 2) void attn_bwd_dkdv_kernel(Ge
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
           float2v a = {sacc[r], sacc[r + 1]};
-          const float2v ml = {-lr[r], -lr[r + 1]}, dl = {dr[r], dr[r + 1]};
+          const float2v ml = {KB ? kb2 - lr[r] : -lr[r], KB ? kb2 - lr[r + 1] : -lr[r + 1]},
+                        dl = {dr[r], dr[r + 1]};
           a = __builtin_elementwise_fma(a, sl, ml);
           float2v pp = {fast_exp2(a.x), fast_exp2(a.y)};
           if (!full) {
@@ -2283,20 +2348,25 @@ inline int bwd_threads(int L) {
   return f64 > f128 + 0.10 ? 128 : 256;
 }
 
-#define ATTN_BWD_LAUNCH2(DH_, NTT_, DR_)                                                          \
+#define ATTN_BWD_LAUNCH2(DH_, NTT_, DR_, KB_)                                                     \
   do {                                                                                            \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DH_, NTT_, DR_>), grid, dim3(NTT_), 0, s, g, m,        \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DH_, NTT_, DR_, KB_>), grid, dim3(NTT_), 0, s, g, m,   \
                        drop_bits, lp, dscale, (const bf16_t*)dout, d_s_b, d_s_t, lse,             \
                        (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv, dq_s_b, dq_s_t,      \
-                       bias_grad);                                                                \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DH_, NTT_, DR_>), grid, dim3(NTT_), 0, s, g, m,      \
+                       bias_grad, key_bias, kb_s_b);                                              \
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DH_, NTT_, DR_, KB_>), grid, dim3(NTT_), 0, s, g, m, \
                        drop_bits_t, lp, dscale, (const bf16_t*)dout, d_s_b, d_s_t, lse, delta,    \
-                       (bf16_t*)dqkv, dq_s_b, dq_s_t, bias_grad);                                 \
+                       (bf16_t*)dqkv, dq_s_b, dq_s_t, bias_grad, key_bias, kb_s_b);               \
   } while (0)
-#define ATTN_BWD_LAUNCH(DH_, NTT_)                     \
-  do {                                                 \
-    if (drop_bits) ATTN_BWD_LAUNCH2(DH_, NTT_, true);  \
-    else ATTN_BWD_LAUNCH2(DH_, NTT_, false);           \
+#define ATTN_BWD_LAUNCH(DH_, NTT_)                                \
+  do {                                                            \
+    if (key_bias) {                                               \
+      if (drop_bits) ATTN_BWD_LAUNCH2(DH_, NTT_, true, true);     \
+      else ATTN_BWD_LAUNCH2(DH_, NTT_, false, true);              \
+    } else {                                                      \
+      if (drop_bits) ATTN_BWD_LAUNCH2(DH_, NTT_, true, false);    \
+      else ATTN_BWD_LAUNCH2(DH_, NTT_, false, false);             \
+    }                                                             \
   } while (0)
 
 #if MMT_RES_ABL == 9
@@ -2321,13 +2391,37 @@ extern "C" int mmt_dropout_bits(const uint32_t* rng, uint32_t layer, uint32_t si
   return MMT_OK;
 }
 
+// key_bias layout of include/mmt_api.h (mmt_attn_fwd_keybias); NULL passes
+static int check_key_bias(const char* fn, const float* key_bias, int64_t kb_s_b, int L, float scale) {
+  if (!key_bias) return MMT_OK;
+  MMT_CHECK_ARG(kb_s_b % 4 == 0 && kb_s_b >= lp_of(L) && (uintptr_t)key_bias % 16 == 0,
+                "%s: key_bias needs 16-B aligned rows of >= roundup(L, 64) = %d floats, stride a "
+                "multiple of 4 (got %lld)", fn, lp_of(L), (long long)kb_s_b);
+  MMT_CHECK_ARG(scale > 0.f, "%s: key_bias needs scale > 0", fn);
+  return MMT_OK;
+}
+
 extern "C" int mmt_attn_fwd(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H, int Dh,
                             float scale, int n_sets, const int32_t* set_start,
                             const int32_t* set_len, const uint32_t* set_vis,
                             const uint32_t* drop_bits, float keep_prob, const float* bias,
                             void* o, int64_t o_s_b, int64_t o_s_t, float* lse, float* wsum,
                             mmt_stream_t stream) {
+  return mmt_attn_fwd_keybias(qkv, s_b, s_t, B, L, H, Dh, scale, n_sets, set_start, set_len,
+                              set_vis, drop_bits, keep_prob, bias, o, o_s_b, o_s_t, lse, wsum,
+                              nullptr, 0, stream);
+}
+
+extern "C" int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H,
+                                    int Dh, float scale, int n_sets, const int32_t* set_start,
+                                    const int32_t* set_len, const uint32_t* set_vis,
+                                    const uint32_t* drop_bits, float keep_prob, const float* bias,
+                                    void* o, int64_t o_s_b, int64_t o_s_t, float* lse, float* wsum,
+                                    const float* key_bias, int64_t kb_s_b, mmt_stream_t stream) {
   MMT_CHECK_ARG(qkv && o && lse, "mmt_attn_fwd: null pointer");
+  MMT_CHECK_ARG(!key_bias || (!wsum && !bias),
+                "mmt_attn_fwd: key_bias cannot be combined with wsum or the additive (H, L, L) bias");
+  if (int kc = check_key_bias("mmt_attn_fwd", key_bias, kb_s_b, L, scale)) return kc;
   MMT_CHECK_ARG(B > 0 && L > 0 && H > 0 && L <= MAXL, "mmt_attn_fwd: bad shape (L <= %d)", MAXL);
   MMT_CHECK_ARG(s_t % 8 == 0 && s_b % 8 == 0 && o_s_t % 4 == 0 && o_s_b % 4 == 0,
                 "mmt_attn_fwd: strides must keep 16-B rows");
@@ -2348,25 +2442,28 @@ extern "C" int mmt_attn_fwd(const void* qkv, int64_t s_b, int64_t s_t, int B, in
     if (res_plan(m, L, plan)) {
       const int ntile = ((L + 63) / 64) * 2;  // even tile counts are instantiated
       const bool one1 = attn_res_enabled("MMT_ATTN_ONEPASS");
-#define RES1(NT_, DR_, WS_)                                                                       \
+#define RES1(NT_, DR_, WS_, KB_)                                                                  \
   do {                                                                                            \
     if (one1)                                                                                     \
-      hipLaunchKernelGGL((attn_fwd_res_kernel<NT_, DR_, WS_, true>), dim3(B * H), dim3(64 * RES_NW), \
-                         0, as_stream(stream), g, m, plan, drop_bits, lp, dscale, (bf16_t*)o, o_s_b, \
-                         o_s_t, lse, wsum);                                                       \
+      hipLaunchKernelGGL((attn_fwd_res_kernel<NT_, DR_, WS_, true, KB_>), dim3(B * H),            \
+                         dim3(64 * RES_NW), 0, as_stream(stream), g, m, plan, drop_bits, lp,      \
+                         dscale, (bf16_t*)o, o_s_b, o_s_t, lse, wsum, key_bias, kb_s_b);          \
     else                                                                                          \
-      hipLaunchKernelGGL((attn_fwd_res_kernel<NT_, DR_, WS_, false>), dim3(B * H), dim3(64 * RES_NW), \
-                         0, as_stream(stream), g, m, plan, drop_bits, lp, dscale, (bf16_t*)o, o_s_b, \
-                         o_s_t, lse, wsum);                                                       \
+      hipLaunchKernelGGL((attn_fwd_res_kernel<NT_, DR_, WS_, false, KB_>), dim3(B * H),           \
+                         dim3(64 * RES_NW), 0, as_stream(stream), g, m, plan, drop_bits, lp,      \
+                         dscale, (bf16_t*)o, o_s_b, o_s_t, lse, wsum, key_bias, kb_s_b);          \
   } while (0)
 #define RES2(NT_)                                          \
   do {                                                     \
-    if (drop_bits) {                                       \
-      if (wsum) RES1(NT_, true, true);                     \
-      else RES1(NT_, true, false);                         \
+    if (key_bias) { /* never with wsum (checked above) */  \
+      if (drop_bits) RES1(NT_, true, false, true);         \
+      else RES1(NT_, false, false, true);                  \
+    } else if (drop_bits) {                                \
+      if (wsum) RES1(NT_, true, true, false);              \
+      else RES1(NT_, true, false, false);                  \
     } else {                                               \
-      if (wsum) RES1(NT_, false, true);                    \
-      else RES1(NT_, false, false);                        \
+      if (wsum) RES1(NT_, false, true, false);             \
+      else RES1(NT_, false, false, false);                 \
     }                                                      \
   } while (0)
       switch (ntile) {
@@ -2388,30 +2485,33 @@ extern "C" int mmt_attn_fwd(const void* qkv, int64_t s_b, int64_t s_t, int B, in
   int nq = g_attn_nq > 0 ? std::min(g_attn_nq, 2) : (L <= 32 ? 1 : L <= 2 * QB ? 2 : L > 32 * RES_TILES ? 2 : 1);
   if (Dh > 64) nq = 1;
   dim3 grid((L + QB * nq - 1) / (QB * nq), H, B);
-#define FWD1(DH_, NQ_, WS_, DR_)                                                                 \
+#define FWD1(DH_, NQ_, WS_, DR_, KB_)                                                            \
   do {                                                                                            \
     bool one_wave = false;                                                                        \
     if constexpr (DH_ <= 64 && NQ_ == 1) {                                                        \
       if (L <= 32) { /* one 32-row block (the T5 text): one-wave workgroups */                    \
         one_wave = true;                                                                          \
-        hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_, 1>), dim3(1, H, B), dim3(64), 0,  \
-                           as_stream(stream), g, m, drop_bits, lp, dscale, bias, (bf16_t*)o,      \
-                           o_s_b, o_s_t, lse, wsum);                                              \
+        hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_, 1, KB_>), dim3(1, H, B),          \
+                           dim3(64), 0, as_stream(stream), g, m, drop_bits, lp, dscale, bias,     \
+                           (bf16_t*)o, o_s_b, o_s_t, lse, wsum, key_bias, kb_s_b);                \
       }                                                                                           \
     }                                                                                             \
     if (!one_wave)                                                                                \
-      hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_>), grid, dim3(NT), 0,                \
+      hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_, 4, KB_>), grid, dim3(NT), 0,        \
                          as_stream(stream), g, m, drop_bits, lp, dscale, bias, (bf16_t*)o, o_s_b,  \
-                         o_s_t, lse, wsum);                                                       \
+                         o_s_t, lse, wsum, key_bias, kb_s_b);                                     \
   } while (0)
 #define FWD(DH_, NQ_)                                          \
   do {                                                         \
-    if (drop_bits) {                                           \
-      if (wsum) FWD1(DH_, NQ_, true, true);                    \
-      else FWD1(DH_, NQ_, false, true);                        \
+    if (key_bias) { /* never with wsum (checked above) */      \
+      if (drop_bits) FWD1(DH_, NQ_, false, true, true);        \
+      else FWD1(DH_, NQ_, false, false, true);                 \
+    } else if (drop_bits) {                                    \
+      if (wsum) FWD1(DH_, NQ_, true, true, false);             \
+      else FWD1(DH_, NQ_, false, true, false);                 \
     } else {                                                   \
-      if (wsum) FWD1(DH_, NQ_, true, false);                   \
-      else FWD1(DH_, NQ_, false, false);                       \
+      if (wsum) FWD1(DH_, NQ_, true, false, false);            \
+      else FWD1(DH_, NQ_, false, false, false);                \
     }                                                          \
   } while (0)
   if (Dh == 64) {
@@ -2434,7 +2534,23 @@ extern "C" int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, in
                             const void* dout, int64_t d_s_b, int64_t d_s_t, const float* lse,
                             float* delta, void* dqkv, int64_t dq_s_b, int64_t dq_s_t,
                             float* bias_grad, mmt_stream_t stream) {
+  return mmt_attn_bwd_keybias(qkv, s_b, s_t, B, L, H, Dh, scale, n_sets, set_start, set_len,
+                              set_vis, drop_bits, drop_bits_t, keep_prob, o, o_s_b, o_s_t, dout,
+                              d_s_b, d_s_t, lse, delta, dqkv, dq_s_b, dq_s_t, bias_grad, nullptr, 0,
+                              stream);
+}
+
+extern "C" int mmt_attn_bwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H,
+                                    int Dh, float scale, int n_sets, const int32_t* set_start,
+                                    const int32_t* set_len, const uint32_t* set_vis,
+                                    const uint32_t* drop_bits, const uint32_t* drop_bits_t,
+                                    float keep_prob, const void* o, int64_t o_s_b, int64_t o_s_t,
+                                    const void* dout, int64_t d_s_b, int64_t d_s_t,
+                                    const float* lse, float* delta, void* dqkv, int64_t dq_s_b,
+                                    int64_t dq_s_t, float* bias_grad, const float* key_bias,
+                                    int64_t kb_s_b, mmt_stream_t stream) {
   MMT_CHECK_ARG(qkv && o && dout && lse && delta && dqkv, "mmt_attn_bwd: null pointer");
+  if (int kc = check_key_bias("mmt_attn_bwd", key_bias, kb_s_b, L, scale)) return kc;
   MMT_CHECK_ARG(B > 0 && L > 0 && H > 0 && L <= MAXL, "mmt_attn_bwd: bad shape");
   MMT_CHECK_ARG(s_t % 8 == 0 && d_s_t % 8 == 0 && dq_s_t % 4 == 0 && o_s_t % 8 == 0,
                 "mmt_attn_bwd: strides must keep 16-B rows");
@@ -2453,7 +2569,10 @@ extern "C" int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, in
     // for bit). Alone (tools/attn_bench.py, B = 512) it wins at L = 292 (464 vs 516 us) and
     // L <= 164 (1.06-1.13x) and loses 0-6 % at L = 196 .. 276 (one workgroup per CU there);
     // in the step it is faster at every L (all: 14.75k, per-L choice: 14.73k, two-phase: 14.66k)
-    const bool bwd8 = attn_res_enabled("MMT_ATTN_BWD8") &&
+    // With a key bias the two-phase kernel always: the concurrent-phase kernel has no key-bias
+    // form (it sits at 255 of its 256 VGPRs and within 0.5 KB of the CU's LDS at L = 312: the
+    // bias would spill; DESIGN.md, proportional attention, for the measured cost of this choice).
+    const bool bwd8 = !key_bias && attn_res_enabled("MMT_ATTN_BWD8") &&
                       res8_need(L, ((L + 63) / 64) * 2) <= res8_lds(((L + 63) / 64) * 2);
     ResPlanB plan;
     if (bwd8 ? res_plan_bwd(m, L, plan, RES8_NA, 2 * RES_NW - RES8_NA) : res_plan_bwd(m, L, plan)) {
@@ -2471,11 +2590,16 @@ extern "C" int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, in
                          m, plan, drop_bits, drop_bits_t, lp, dscale, (const bf16_t*)dout, d_s_b,   \
                          d_s_t, lse, (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv, dq_s_b, \
                          dq_s_t, bias_grad);                                                        \
+    else if (key_bias)                                                                              \
+      hipLaunchKernelGGL((attn_bwd_res_kernel<NT_, DR_, true>), dim3(B * H), dim3(64 * RES_NW), 0,  \
+                         s, g, m, plan, drop_bits, drop_bits_t, lp, dscale, (const bf16_t*)dout,    \
+                         d_s_b, d_s_t, lse, (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv,  \
+                         dq_s_b, dq_s_t, bias_grad, key_bias, kb_s_b);                              \
     else                                                                                            \
-      hipLaunchKernelGGL((attn_bwd_res_kernel<NT_, DR_>), dim3(B * H), dim3(64 * RES_NW), 0, s, g,  \
-                         m, plan, drop_bits, drop_bits_t, lp, dscale, (const bf16_t*)dout, d_s_b,   \
-                         d_s_t, lse, (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv, dq_s_b, \
-                         dq_s_t, bias_grad);                                                        \
+      hipLaunchKernelGGL((attn_bwd_res_kernel<NT_, DR_, false>), dim3(B * H), dim3(64 * RES_NW), 0, \
+                         s, g, m, plan, drop_bits, drop_bits_t, lp, dscale, (const bf16_t*)dout,    \
+                         d_s_b, d_s_t, lse, (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv,  \
+                         dq_s_b, dq_s_t, bias_grad, key_bias, kb_s_b);                              \
   } while (0)
 #define RESB2(NT_)                  \
   do {                              \

@@ -1351,3 +1351,34 @@ extern "C" int mmt_tome_merge_wavg_bwd(const void* g_out, int dtype, int n, int 
   MMT_CHECK_LAUNCH("mmt_tome_merge_wavg_bwd");
   return MMT_OK;
 }
+
+// ------------------------------------------------------------ proportional attention's key bias
+// kb[b, set_start + j] = logf(size[b, j]) (j < t): the additive logit of mmt_attn_fwd_keybias that
+// lets a merged token vote as the size[b, j] patches it stands for. zero_rest: every other entry
+// of [0, roundup(L, 64)) is written 0 (unmerged sets and the padding the kernels load past L).
+namespace {
+__global__ void tome_size_bias_kernel(const float* __restrict__ size, int t, int set_start, int lp,
+                                      float* __restrict__ kb, int64_t kb_s_b, int zero_rest) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // position in the row
+  const int j = i - set_start;
+  if (j >= 0 && j < t)
+    kb[(int64_t)b * kb_s_b + i] = logf(size[(int64_t)b * t + j]);
+  else if (zero_rest && i < lp)
+    kb[(int64_t)b * kb_s_b + i] = 0.f;
+}
+}  // namespace
+
+extern "C" int mmt_tome_size_bias(const float* size, int B, int t, int set_start, int L, float* kb,
+                                  int64_t kb_s_b, int zero_rest, mmt_stream_t stream) {
+  MMT_CHECK_ARG(size && kb, "mmt_tome_size_bias: null pointer");
+  MMT_CHECK_ARG(B > 0 && L > 0 && t > 0 && set_start >= 0 && set_start + t <= L,
+                "mmt_tome_size_bias: bad shape");
+  const int lp = (L + 63) & ~63;
+  MMT_CHECK_ARG(kb_s_b >= (zero_rest ? lp : L), "mmt_tome_size_bias: kb rows shorter than %d",
+                zero_rest ? lp : L);
+  hipLaunchKernelGGL(tome_size_bias_kernel, dim3(lp / 64, B), dim3(64), 0, as_stream(stream), size,
+                     t, set_start, lp, kb, kb_s_b, zero_rest);
+  MMT_CHECK_LAUNCH("mmt_tome_size_bias");
+  return MMT_OK;
+}

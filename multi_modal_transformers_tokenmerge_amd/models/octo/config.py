@@ -54,6 +54,16 @@ class OctoConfig:
     # (per-set top-k on the attention importance, compressed_attention.py:302-308 +
     # token_compression.py:15-46, every set); YAML key token_compression_method
     compression: str = "tome"
+    # ToMe proportional attention (YAML key proportional_attention): from the second block on,
+    # softmax(q.k * scale + log size[k]) with the token sizes the merges carry, so a merged token
+    # votes as the patches it stands for (a per-key bias inside the attention kernels). Needs
+    # compression == "tome" (pruning carries no sizes); a no-op without token_compression_sequence
+    proportional_attention: bool = False
+
+    def __post_init__(self):
+        if self.proportional_attention and self.compression != "tome":
+            raise ValueError(f"proportional_attention needs compression='tome' (token sizes), got "
+                             f"{self.compression!r}")
 
     @property
     def tome_r(self) -> int:
@@ -74,6 +84,10 @@ PRESETS = {
     "octo-small": OctoConfig(),
     # configs[2]: small, ToMe r=16 per block (BASELINE metric config)
     "octo-small-tome16": OctoConfig(name="octo-small-tome16", token_compression_sequence=TOME16),
+    # configs[2] with proportional attention (log token size on the keys from block 1 on)
+    "octo-small-tome16-prop": OctoConfig(name="octo-small-tome16-prop",
+                                         token_compression_sequence=TOME16,
+                                         proportional_attention=True),
     # configs[3]: base, 2 cameras, 2-step history
     "octo-base-2cam": OctoConfig(
         name="octo-base-2cam", token_embedding_dim=768, num_heads=12, mlp_dim=3072,

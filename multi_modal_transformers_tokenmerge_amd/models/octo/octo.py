@@ -191,9 +191,15 @@ class Octo:
             self.readout_group_counts = torch.full((A,), per, dtype=torch.int32, device=self.device)
 
     def layer_ctxs(self, train: bool, rng, sample_offset: int) -> List[LayerCtx]:
-        return [LayerCtx(layer=i, sets=s, table=t, tome_set=ts, r=r, prune=pr, train=train, rng=rng,
-                         sample_offset=sample_offset, tome_plan=plan)
-                for i, (s, t, ts, r, pr, plan) in enumerate(self.layer_sets)]
+        prop = bool(self.cfg.proportional_attention)
+        ctxs, carried = [], -1  # carried: the set whose sizes the last single-set merge handed on
+        for i, (s, t, ts, r, pr, plan) in enumerate(self.layer_sets):
+            ctxs.append(LayerCtx(layer=i, sets=s, table=t, tome_set=ts, r=r, prune=pr, train=train,
+                                 rng=rng, sample_offset=sample_offset, tome_plan=plan,
+                                 prop_attn=prop, size_set=carried))
+            if len(plan) == 1:
+                carried = plan[0][0]
+        return ctxs
 
     # ------------------------------------------------------------------ forward / backward
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
