@@ -476,7 +476,8 @@ int mmt_patch_positions(const uint32_t* rng, uint32_t site, int B, int I, int Hi
  * | readout_pe[j]  (row_src[l] = kind << 24 | j, kind 0 text / 1 image / 2 readout):
  * TokenSequence.assemble_embeddings (token_sequencer.py:255-269), readout AddPositionEmbedding
  * on zeros (readout.py:18-33, octo.py:103-108), ImageTokenizer embeddings (:300-307) and the
- * encoder's learned position embedding (attention.py:71-85,97-100), fused. fp32 tables. */
+ * encoder's learned position embedding (attention.py:71-85,97-100), fused. fp32 tables.
+ * D > 0, D % 8 == 0; text, img and x0 are read / written as 16-B vectors: 16-B aligned bases. */
 int mmt_seq_assemble_fwd(int B, int L, int D, const int32_t* row_src, const void* text, int T,
                          const void* img, int NI, const int32_t* rtok, const int32_t* ctok,
                          const float* row_emb, const float* col_emb, const float* readout_pe,
@@ -484,7 +485,8 @@ int mmt_seq_assemble_fwd(int B, int L, int D, const int32_t* row_src, const void
 /* backward: gathers d(text), d(img) (bf16) from the fp32 dx0, accumulates d(readout_pe) and the
  * (Q, D) row/col embedding gradients (LDS histograms per 64-column slice, then one global
  * atomic per table entry). img_rows[j] = sequence row of image token j. d(pe) is mmt_colsum
- * over the batch. */
+ * over the batch. dtext NULL: the text rows are skipped (frozen text encoder). D > 0,
+ * D % 8 == 0; dx0, dtext and dimg are 16-B vectors: 16-B aligned bases. */
 int mmt_seq_assemble_bwd(int B, int L, int D, const int32_t* row_src, const void* dx0,
                          void* dtext, int T, void* dimg, int NI, const int32_t* rtok,
                          const int32_t* ctok, const int32_t* img_rows, int Q, float* drow_emb,
@@ -505,17 +507,21 @@ int mmt_patch_embed_grad(int B, int L, int D, int I, int Himg, int P, int Q,
  * dout viewed as (B, L*D). The training step fuses this add into mmt_seq_assemble_fwd. */
 int mmt_add_position_embedding(const float* x, const float* pe, float* out, int B, int L, int D,
                                mmt_stream_t stream);
-/* readout gather + mean (octo.py:122-124, diffusion.py:102): out[b] = mean_i x[b, rows[i]]. */
+/* readout gather + mean (octo.py:122-124, diffusion.py:102): out[b] = mean_i x[b, rows[i]]
+ * (x fp32 with element strides xs_b, xs_t; out bf16, row stride ld_out; B, D, nrows > 0). */
 int mmt_rows_mean_fwd(const void* x, int64_t xs_b, int64_t xs_t, int B, int D,
                       const int32_t* rows, int nrows, void* out, int64_t ld_out,
                       mmt_stream_t stream);
+/* backward: writes the whole contiguous fp32 dx (B, L, D), no zeroing needed first: de[b] / nrows
+ * in the rows with row_flag[l] >= 0, 0 in every other row (de bf16, row stride ld_de). */
 int mmt_rows_mean_bwd(const void* de, int64_t ld_de, int B, int L, int D, const int32_t* row_flag,
                       int nrows, void* dx, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ diffusion head
  * DiffusionActionHead.denoise_loss (diffusion.py:110-143) pieces: t ~ U{0..steps-1}, eps ~ N(0,1)
  * (or injected), noisy = sqrt(abar_t) a + sqrt(1-abar_t) eps written to cat[:, :A] (bf16),
- * FourierFeatures (:41-51) [cos 2 pi t W, sin 2 pi t W] (bf16 (B, 2F)). */
+ * FourierFeatures (:41-51) [cos 2 pi t W, sin 2 pi t W] (bf16 (B, 2F)). steps, A, F > 0,
+ * ld_cat >= A. */
 int mmt_diffusion_prep(const uint32_t* rng, int B, int A, int steps, int64_t sample_offset,
                        const float* actions, const float* alpha_hats, const float* fourier_w,
                        int F, const int32_t* t_in, const float* eps_in, int32_t* t_out,
@@ -523,7 +529,8 @@ int mmt_diffusion_prep(const uint32_t* rng, int B, int A, int steps, int64_t sam
                        mmt_stream_t stream);
 int mmt_fourier_bwd(const void* dfeats, int B, int F, const int32_t* t, const float* fourier_w,
                     float* dw, mmt_stream_t stream);
-/* optax.l2_loss summed over actions, mean over batch; dpred = (pred-eps)*grad_scale/B (bf16). */
+/* optax.l2_loss summed over actions, mean over batch; dpred = (pred-eps)*grad_scale/B (bf16,
+ * (B, A) contiguous). loss[0] is overwritten, not accumulated. ld_pred >= A, B * A fits int. */
 int mmt_diffusion_loss(const float* pred, int64_t ld_pred, const float* eps, int B, int A,
                        float grad_scale, float* loss, void* dpred, mmt_stream_t stream);
 /* DiffusionActionHead.predict_action (diffusion.py:146-209), SURVEY §8f row 2: all `steps`
@@ -566,7 +573,9 @@ int mmt_action_head(int kind, const float* z, int64_t ldz, int R, int N, const f
 
 /* ------------------------------------------------------------------ T5 encoder pieces
  * (tokenizers/text/t5_base.py:8-15, frozen FlaxT5 encoder): T5LayerNorm and the shared
- * embedding lookup. */
+ * embedding lookup. bf16 rows of D elements, D > 0, D % 8 == 0, moved as 16-B vectors: x, w, y
+ * (table, out) have 16-B aligned bases. The gather clamps ids to [0, vocab - 1] (id < 0 reads
+ * row 0, id >= vocab reads row vocab - 1), as jnp.take does in the reference. */
 int mmt_rmsnorm_fwd(const void* x, int64_t rows, int D, const void* w, float eps, void* y,
                     mmt_stream_t stream);
 int mmt_embedding_gather(const int32_t* ids, int64_t n, int D, const void* table, int vocab,

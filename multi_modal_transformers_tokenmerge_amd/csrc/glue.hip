@@ -429,7 +429,7 @@ __global__ void fourier_bwd_kernel(const bf16_t* __restrict__ dfeats, int B, int
 }
 
 // loss = mean_b sum_j 0.5 (pred - eps)^2 (optax.l2_loss, diffusion.py:141-142);
-// dpred = (pred - eps) * grad_scale / B  (bf16). One workgroup.
+// dpred = (pred - eps) * grad_scale / B  (bf16). One workgroup; loss[0] is overwritten.
 __global__ void diffusion_loss_kernel(const float* __restrict__ pred, int64_t ld_pred,
                                       const float* __restrict__ eps, int B, int A,
                                       float grad_scale, float* __restrict__ loss,
@@ -513,6 +513,8 @@ __global__ void rmsnorm_fwd_kernel(const bf16_t* __restrict__ x, int64_t rows, i
   }
 }
 
+// out[r, :] = table[clamp(ids[r], 0, vocab - 1), :] (jnp.take's clamp: no id forms an address
+// outside the table), one 16-B vector per thread
 __global__ void embedding_gather_kernel(const int32_t* __restrict__ ids, int64_t n, int D,
                                         const bf16_t* __restrict__ table, int vocab,
                                         bf16_t* __restrict__ out) {
@@ -764,7 +766,10 @@ extern "C" int mmt_seq_assemble_fwd(int B, int L, int D, const int32_t* row_src,
                                     const int32_t* ctok, const float* row_emb, const float* col_emb,
                                     const float* readout_pe, const float* pe, void* x0,
                                     mmt_stream_t stream) {
-  MMT_CHECK_ARG(row_src && x0 && pe && D % 8 == 0 && B > 0 && L > 0, "mmt_seq_assemble_fwd: args");
+  MMT_CHECK_ARG(row_src && x0 && pe && D > 0 && D % 8 == 0 && B > 0 && L > 0,
+                "mmt_seq_assemble_fwd: args (D > 0, D %% 8 == 0)");
+  MMT_CHECK_ARG((uintptr_t)text % 16 == 0 && (uintptr_t)img % 16 == 0 && (uintptr_t)x0 % 16 == 0,
+                "mmt_seq_assemble_fwd: text, img and x0 must be 16-B aligned");
   const int64_t n = (int64_t)B * L * (D / 8);
   hipLaunchKernelGGL(seq_assemble_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0,
                      as_stream(stream), B, L, D, row_src, (const bf16_t*)text, T,
@@ -779,7 +784,10 @@ extern "C" int mmt_seq_assemble_bwd(int B, int L, int D, const int32_t* row_src,
                                     const int32_t* ctok, const int32_t* img_rows, int Q,
                                     float* drow_emb, float* dcol_emb, float* dreadout_pe,
                                     mmt_stream_t stream) {
-  MMT_CHECK_ARG(row_src && dx0 && D % 8 == 0 && B > 0 && L > 0, "mmt_seq_assemble_bwd: args");
+  MMT_CHECK_ARG(row_src && dx0 && D > 0 && D % 8 == 0 && B > 0 && L > 0,
+                "mmt_seq_assemble_bwd: args (D > 0, D %% 8 == 0)");
+  MMT_CHECK_ARG((uintptr_t)dx0 % 16 == 0 && (uintptr_t)dtext % 16 == 0 && (uintptr_t)dimg % 16 == 0,
+                "mmt_seq_assemble_bwd: dx0, dtext and dimg must be 16-B aligned");
   // drow_emb = dcol_emb = NULL: the image tokens' gradients only (the position-embedding
   // gradients then come from mmt_patch_embed_grad)
   const bool emb = drow_emb || dcol_emb;
@@ -839,7 +847,7 @@ extern "C" int mmt_patch_embed_grad(int B, int L, int D, int I, int Himg, int P,
 extern "C" int mmt_rows_mean_fwd(const void* x, int64_t xs_b, int64_t xs_t, int B, int D,
                                  const int32_t* rows, int nrows, void* out, int64_t ld_out,
                                  mmt_stream_t stream) {
-  MMT_CHECK_ARG(x && rows && out && B > 0 && nrows > 0, "mmt_rows_mean_fwd: args");
+  MMT_CHECK_ARG(x && rows && out && B > 0 && D > 0 && nrows > 0, "mmt_rows_mean_fwd: args");
   hipLaunchKernelGGL(rows_mean_fwd_kernel, dim3(B), dim3(256), 0, as_stream(stream),
                      (const float*)x, xs_b, xs_t, D, rows, nrows, (bf16_t*)out, ld_out);
   MMT_CHECK_LAUNCH("mmt_rows_mean_fwd");
@@ -848,7 +856,8 @@ extern "C" int mmt_rows_mean_fwd(const void* x, int64_t xs_b, int64_t xs_t, int 
 
 extern "C" int mmt_rows_mean_bwd(const void* de, int64_t ld_de, int B, int L, int D,
                                  const int32_t* row_flag, int nrows, void* dx, mmt_stream_t stream) {
-  MMT_CHECK_ARG(de && row_flag && dx && B > 0 && nrows > 0, "mmt_rows_mean_bwd: args");
+  MMT_CHECK_ARG(de && row_flag && dx && B > 0 && L > 0 && D > 0 && nrows > 0,
+                "mmt_rows_mean_bwd: args");
   const int64_t n = (int64_t)B * L * D;
   hipLaunchKernelGGL(rows_mean_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      (const bf16_t*)de, ld_de, B, L, D, row_flag, nrows, (float*)dx);
@@ -913,6 +922,9 @@ extern "C" int mmt_diffusion_prep(const uint32_t* rng, int B, int A, int steps,
   MMT_CHECK_ARG(actions && alpha_hats && fourier_w && t_out && eps_out && cat && feats && B > 0,
                 "mmt_diffusion_prep: args");
   MMT_CHECK_ARG((t_in && eps_in) || rng, "mmt_diffusion_prep: need rng or injected (t, eps)");
+  MMT_CHECK_ARG(steps > 0 && A > 0 && F > 0 && ld_cat >= A,
+                "mmt_diffusion_prep: steps %d, A %d, F %d must be positive, ld_cat %lld >= A", steps,
+                A, F, (long long)ld_cat);
   hipLaunchKernelGGL(diffusion_prep_kernel, dim3(B), dim3(256), 0, as_stream(stream), rng, B, A,
                      steps, sample_offset, actions, alpha_hats, fourier_w, F, t_in, eps_in, t_out,
                      eps_out, (bf16_t*)cat, ld_cat, (bf16_t*)feats);
@@ -934,6 +946,9 @@ extern "C" int mmt_diffusion_loss(const float* pred, int64_t ld_pred, const floa
                                   int A, float grad_scale, float* loss, void* dpred,
                                   mmt_stream_t stream) {
   MMT_CHECK_ARG(pred && eps && loss && dpred && B > 0 && A > 0, "mmt_diffusion_loss: args");
+  MMT_CHECK_ARG(ld_pred >= A, "mmt_diffusion_loss: ld_pred %lld < A %d", (long long)ld_pred, A);
+  MMT_CHECK_ARG((int64_t)B * A <= INT32_MAX, "mmt_diffusion_loss: B * A = %lld overflows int",
+                (long long)B * A);
   hipLaunchKernelGGL(diffusion_loss_kernel, dim3(1), dim3(1024), 0, as_stream(stream), pred,
                      ld_pred, eps, B, A, grad_scale, loss, (bf16_t*)dpred);
   MMT_CHECK_LAUNCH("mmt_diffusion_loss");
@@ -942,7 +957,10 @@ extern "C" int mmt_diffusion_loss(const float* pred, int64_t ld_pred, const floa
 
 extern "C" int mmt_rmsnorm_fwd(const void* x, int64_t rows, int D, const void* w, float eps,
                                void* y, mmt_stream_t stream) {
-  MMT_CHECK_ARG(x && w && y && rows > 0 && D % 8 == 0, "mmt_rmsnorm_fwd: args");
+  MMT_CHECK_ARG(x && w && y && rows > 0 && D > 0 && D % 8 == 0,
+                "mmt_rmsnorm_fwd: args (D > 0, D %% 8 == 0)");
+  MMT_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)y % 16 == 0,
+                "mmt_rmsnorm_fwd: x, w and y must be 16-B aligned");
   hipLaunchKernelGGL(rmsnorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, as_stream(stream),
                      (const bf16_t*)x, rows, D, (const bf16_t*)w, eps, (bf16_t*)y);
   MMT_CHECK_LAUNCH("mmt_rmsnorm_fwd");
@@ -951,7 +969,10 @@ extern "C" int mmt_rmsnorm_fwd(const void* x, int64_t rows, int D, const void* w
 
 extern "C" int mmt_embedding_gather(const int32_t* ids, int64_t n, int D, const void* table,
                                     int vocab, void* out, mmt_stream_t stream) {
-  MMT_CHECK_ARG(ids && table && out && n > 0 && D % 8 == 0 && vocab > 0, "mmt_embedding_gather: args");
+  MMT_CHECK_ARG(ids && table && out && n > 0 && D > 0 && D % 8 == 0 && vocab > 0,
+                "mmt_embedding_gather: args (D > 0, D %% 8 == 0)");
+  MMT_CHECK_ARG((uintptr_t)table % 16 == 0 && (uintptr_t)out % 16 == 0,
+                "mmt_embedding_gather: table and out must be 16-B aligned");
   const int64_t t = n * (D / 8);
   hipLaunchKernelGGL(embedding_gather_kernel, dim3((t + 255) / 256), dim3(256), 0,
                      as_stream(stream), ids, n, D, (const bf16_t*)table, vocab, (bf16_t*)out);
