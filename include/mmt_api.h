@@ -47,7 +47,8 @@ int mmt_version(void);
 
 /* Device-side index checks. The entry points that address memory through caller-supplied index
  * arrays (mmt_tome_merge_wavg_fwd / _bwd, mmt_tome_merge_seqnorm_fwd, mmt_ln_unmerge_dropout_bwd,
- * mmt_gather_rows, mmt_topk_scatter_bwd) cannot see those device values at launch. Their kernels
+ * mmt_gather_rows, mmt_topk_scatter_bwd, mmt_tome_pos_map, mmt_tome_source_step / _groups,
+ * mmt_tome_unmerge_fwd / _bwd) cannot see those device values at launch. Their kernels
  * range-check every index they use; an invalid one is replaced by 0 (so no access leaves its
  * tensor and the context survives) and sets a bit of a library-wide device status word:
  *   MMT_FAULT_TOME_INDEX     unm / src not in [0, ceil(t/2)), dst not in [0, t/2)
@@ -158,6 +159,47 @@ int mmt_tome_merge_wavg_bwd(const void* g_out, int dtype, int n, int L, int D, i
                             const float* size_out, const int32_t* pos_map, void* g_in,
                             int64_t gi_s_n, int64_t gi_s_t, mmt_stream_t stream);
 
+/* ---- merge source and unmerge. Replaces ToMe's merge_source (the patch -> merged token map the
+ * reference's merge closure, token_compression.py:90-129, never exposes) and adds the unmerge it
+ * implies. All five are graph-capturable and allocate nothing; index values are range-checked on
+ * the device (see "Device-side index checks" above: clamped to 0 and reported, never followed).
+ *
+ * mmt_tome_pos_map: the (n, t) int32 pos_map that mmt_tome_merge_wavg_fwd writes for the same
+ * unm / src / dst and flags (class / distill layouts included; token_compression.py:90-109's
+ * concat[unm, dst] placement), without touching any x. Same limits on t and r as the merge. */
+int mmt_tome_pos_map(const int32_t* unm_idx, const int32_t* src_idx, const int32_t* dst_idx, int n,
+                     int t, int r, int flags, int32_t* pos_map, mmt_stream_t stream);
+/* One layer of ToMe's merge_source, in place on source (n, t0) int32:
+ * source[b, p] = pos_map[b, source[b, p]] for the layer's pos_map (n, t) -> [0, t - r).
+ * first != 0 starts from the identity (source[b, p] = pos_map[b, p]; needs t0 == t).
+ * source values outside [0, t): MMT_FAULT_ROW_INDEX; pos_map values outside [0, t - r):
+ * MMT_FAULT_POS_MAP. t <= t0 <= 2048 (mmt_tome_match's limit). */
+int mmt_tome_source_step(const int32_t* pos_map, int n, int t, int r, int32_t* source, int t0,
+                         int first, mmt_stream_t stream);
+/* The inverse of source (n, t0) -> [0, tf) in CSR form (ToMe's merge_source matrix, sparse):
+ * group_start (n, tf + 1) int32, members (n, t0) int32; merged token j of sample b stands for the
+ * patches members[b, group_start[b, j] .. group_start[b, j + 1]), listed in ascending patch
+ * order whatever the scheduling. Empty groups are legal. source values outside [0, tf):
+ * MMT_FAULT_ROW_INDEX. tf <= t0 <= 2048. */
+int mmt_tome_source_groups(const int32_t* source, int n, int t0, int tf, int32_t* group_start,
+                           int32_t* members, mmt_stream_t stream);
+/* Unmerge: x (n, L, D) holds a merged set of tf rows at [set_start, set_start + tf); out
+ * (n, L - tf + t0, D) holds rows [0, set_start) copied, then the t0 rows
+ * out[b, set_start + p] = x[b, set_start + source[b, p]], then the remaining rows copied (the
+ * sequence layout of mmt_tome_merge_wavg_fwd, read backwards). fp32 / bf16, D % 8 == 0, strides
+ * and base pointers multiples of 16 bytes. source outside [0, tf): MMT_FAULT_ROW_INDEX. */
+int mmt_tome_unmerge_fwd(const void* x, int dtype, int n, int L, int D, int64_t x_s_n,
+                         int64_t x_s_t, int set_start, int tf, const int32_t* source, int t0,
+                         void* out, int64_t o_s_n, int64_t o_s_t, mmt_stream_t stream);
+/* Its adjoint: g (n, L - tf + t0, D) -> g_x (n, L, D); copied rows copied, set row j = the sum of
+ * g[b, set_start + p] over p in members(j) (mmt_tome_source_groups), accumulated in fp32 in that
+ * (ascending) order and rounded once at the store; an empty group gives zeros. No atomics: the
+ * result is bitwise reproducible. members outside [0, t0) and group_start rows that are not
+ * 0 <= start <= end <= t0: MMT_FAULT_ROW_INDEX. */
+int mmt_tome_unmerge_bwd(const void* g, int dtype, int n, int L, int D, int64_t g_s_n,
+                         int64_t g_s_t, int set_start, int tf, const int32_t* group_start,
+                         const int32_t* members, int t0, void* g_x, int64_t gx_s_n,
+                         int64_t gx_s_t, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ top-k token pruning
  * mmt_topk_gather replaces tokenizers/token_compression.py:15-46 (compute_top_k_tokens, vmapped

@@ -63,6 +63,11 @@ SIGNATURES: dict[str, list] = {
     "mmt_attn_bwd_keybias": [P, L, L, I, I, I, I, F, I, P, P, P, P, P, F, P, L, L, P, L, L, P, P, P,
                              L, L, P, P, L, P],
     "mmt_tome_size_bias": [P, I, I, I, I, P, L, I, P],
+    "mmt_tome_pos_map": [P, P, P, I, I, I, I, P, P],
+    "mmt_tome_source_step": [P, I, I, I, P, I, I, P],
+    "mmt_tome_source_groups": [P, I, I, I, P, P, P],
+    "mmt_tome_unmerge_fwd": [P, I, I, I, I, L, L, I, I, P, I, P, L, L, P],
+    "mmt_tome_unmerge_bwd": [P, I, I, I, I, L, L, I, I, P, P, I, P, L, L, P],
     "mmt_dropout_bits": [P, U32, U32, I, I, F, P, P, P],
     "mmt_seqnorm_fwd": [P, I, L, L, I, I, I, P, P, F, P, L, L, P, P, P],
     "mmt_seqnorm_bwd": [P, I, L, L, P, I, L, L, I, I, I, P, P, P, P, L, L, P, L, L, P, P, P],

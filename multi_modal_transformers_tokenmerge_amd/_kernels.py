@@ -144,6 +144,123 @@ def tome_merge_bwd(g_out: torch.Tensor, set_start: int, t: int, r: int, pos_map:
     return out
 
 
+def _check_i32(a: torch.Tensor, shape, what: str):
+    if tuple(a.shape) != tuple(shape) or a.dtype != torch.int32 or not a.is_contiguous():
+        raise ValueError(f"{what} must be contiguous int32 {tuple(shape)}, got "
+                         f"{a.dtype} {tuple(a.shape)}")
+
+
+def tome_pos_map(unm, src, dst, t: int, r: int, flags: int = 0,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """The (n, t) int32 pos_map tome_merge_fwd writes for the same indices and flags (set token ->
+    merged row of the set), without a merge."""
+    _dev(unm, src, dst, out)
+    n = src.shape[0]
+    for a, shape, what in ((unm, (n, (t + 1) // 2 - r), "unm"), (src, (n, r), "src"),
+                           (dst, (n, r), "dst")):
+        _check_i32(a, shape, what)
+    if out is None:
+        out = torch.empty((n, t), dtype=torch.int32, device=src.device)
+    _check_i32(out, (n, t), "pos_map")
+    _C.call("mmt_tome_pos_map", ptr(unm), ptr(src), ptr(dst), n, t, r, flags, ptr(out),
+            _C.stream_ptr())
+    return out
+
+
+def tome_source_step(pos_map: torch.Tensor, r: int, source: torch.Tensor,
+                     first: bool = False) -> torch.Tensor:
+    """One merge layer of ToMe's merge_source, in place: source[b, p] = pos_map[b, source[b, p]]
+    (first: source[b, p] = pos_map[b, p], the identity start). pos_map (n, t) -> [0, t - r),
+    source (n, t0) int32. Returns source."""
+    _dev(pos_map, source)
+    if pos_map.dim() != 2 or source.dim() != 2:
+        raise ValueError("pos_map must be (n, t) and source (n, t0)")
+    n, t = pos_map.shape
+    t0 = source.shape[1]
+    _check_i32(pos_map, (n, t), "pos_map")
+    _check_i32(source, (n, t0), "source")
+    if first and t0 != t:
+        raise ValueError(f"the identity start needs t0 == t, got t0={t0}, t={t}")
+    _C.call("mmt_tome_source_step", ptr(pos_map), n, t, r, ptr(source), t0, int(bool(first)),
+            _C.stream_ptr())
+    return source
+
+
+def tome_source_groups(source: torch.Tensor, tf: int):
+    """The inverse of source (n, t0) -> [0, tf) in CSR form: (group_start (n, tf + 1), members
+    (n, t0)) int32, each group's patches in ascending order."""
+    _dev(source)
+    if source.dim() != 2:
+        raise ValueError("source must be (n, t0)")
+    n, t0 = source.shape
+    _check_i32(source, (n, t0), "source")
+    group_start = torch.empty((n, tf + 1), dtype=torch.int32, device=source.device)
+    members = torch.empty((n, t0), dtype=torch.int32, device=source.device)
+    _C.call("mmt_tome_source_groups", ptr(source), n, t0, tf, ptr(group_start), ptr(members),
+            _C.stream_ptr())
+    return group_start, members
+
+
+def _check_seq16(x: torch.Tensor, what: str):
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError(f"{what} must be (n, L, D) with unit stride along D")
+    _dtype_code(x)
+    if x.shape[2] % 8:
+        raise ValueError(f"{what}: D={x.shape[2]} must be a multiple of 8")
+    if (x.stride(0) * x.element_size()) % 16 or (x.stride(1) * x.element_size()) % 16 \
+            or x.data_ptr() % 16:
+        raise ValueError(f"{what}: strides and base must be multiples of 16 bytes")
+
+
+def tome_unmerge_fwd(x: torch.Tensor, set_start: int, tf: int, source: torch.Tensor,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """x (n, L, D) with a merged set of tf rows at set_start -> (n, L - tf + t0, D): the set's rows
+    expanded to out[b, set_start + p] = x[b, set_start + source[b, p]], the others copied."""
+    _dev(x, source, out)
+    _check_seq16(x, "x")
+    n, L, D = x.shape
+    if source.dim() != 2:
+        raise ValueError("source must be (n, t0)")
+    t0 = source.shape[1]
+    _check_i32(source, (n, t0), "source")
+    if not (0 <= set_start and 0 < tf <= t0 and set_start + tf <= L):
+        raise ValueError("token set out of range")
+    if out is None:
+        out = torch.empty((n, L - tf + t0, D), dtype=x.dtype, device=x.device)
+    _check_seq16(out, "out")
+    if tuple(out.shape) != (n, L - tf + t0, D) or out.dtype != x.dtype:
+        raise ValueError(f"out must be {x.dtype} {(n, L - tf + t0, D)}")
+    _C.call("mmt_tome_unmerge_fwd", ptr(x), _dtype_code(x), n, L, D, x.stride(0), x.stride(1),
+            set_start, tf, ptr(source), t0, ptr(out), out.stride(0), out.stride(1), _C.stream_ptr())
+    return out
+
+
+def tome_unmerge_bwd(g: torch.Tensor, set_start: int, tf: int, group_start: torch.Tensor,
+                     members: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The adjoint of tome_unmerge_fwd: g (n, L - tf + t0, D) -> (n, L, D); set row j = the fp32
+    sum of its group's rows of g in ascending patch order (tome_source_groups), no atomics."""
+    _dev(g, group_start, members, out)
+    _check_seq16(g, "g")
+    n, Lg, D = g.shape
+    if members.dim() != 2:
+        raise ValueError("members must be (n, t0)")
+    t0 = members.shape[1]
+    _check_i32(members, (n, t0), "members")
+    _check_i32(group_start, (n, tf + 1), "group_start")
+    L = Lg - t0 + tf
+    if not (0 <= set_start and 0 < tf <= t0 and set_start + tf <= L):
+        raise ValueError("token set out of range")
+    if out is None:
+        out = torch.empty((n, L, D), dtype=g.dtype, device=g.device)
+    _check_seq16(out, "out")
+    if tuple(out.shape) != (n, L, D) or out.dtype != g.dtype:
+        raise ValueError(f"out must be {g.dtype} {(n, L, D)}")
+    _C.call("mmt_tome_unmerge_bwd", ptr(g), _dtype_code(g), n, L, D, g.stride(0), g.stride(1),
+            set_start, tf, ptr(group_start), ptr(members), t0, ptr(out), out.stride(0),
+            out.stride(1), _C.stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------ GEMM
 OUT_BF16, OUT_F32, OUT_F32_ACCUM = 0, 1, 2
 ACT_NONE, ACT_RELU = 0, 1

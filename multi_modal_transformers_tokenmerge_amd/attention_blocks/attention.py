@@ -61,6 +61,8 @@ class LayerCtx:
     prop_attn: bool = False        # proportional attention: + log(size) on the keys of merged sets
     size_set: int = -1             # set of the incoming single-tensor `size` when this block merges
     #                                none itself (else: the block's merged set)
+    track_source: bool = False     # merge source: compose every merge's pos_map into the set's
+    #                                patch -> merged token map (OctoConfig.track_merge_source)
 
     def tome_sets(self):
         """The merged sets as ((set index, r), ...)."""
@@ -277,7 +279,10 @@ class Encoder1DBlock(Bindable):
         return _EncoderBlockFn.apply(x, self, ctx), None
 
     # ------------------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, ctx: LayerCtx, size: Optional[torch.Tensor]):
+    def forward(self, x: torch.Tensor, ctx: LayerCtx, size: Optional[torch.Tensor],
+                sources: Optional[dict] = None):
+        """sources (LayerCtx.track_source): {set index: (B, t0) int32 merge-source buffer},
+        updated in place right after that set's merge (the stack allocates them)."""
         B, L, D = x.shape
         H, Dh = self.H, self.Dh
         train = ctx.train
@@ -359,6 +364,13 @@ class Encoder1DBlock(Bindable):
         tome_sets = []
         new_size = size
         ln1_done = None
+
+        def track(si, t_set, r_set, pos_map):
+            # one small launch on the main stream, in place on the set's buffer: part of the
+            # forward, so a captured step replays it (the first merge of a set starts the map)
+            if ctx.track_source and sources is not None:
+                buf = sources[si]
+                K.tome_source_step(pos_map, r_set, buf, first=buf.shape[1] == t_set)
         if ctx.r > 0 and multi:
             # several merged sets: one merge per set, the last set first so the earlier sets'
             # starts stay valid; sizes carried per set ({set index: (B, t) sizes}); LayerNorm_1
@@ -370,6 +382,7 @@ class Encoder1DBlock(Bindable):
                 s0, t = ctx.sets.starts[si], ctx.sets.lens[si]
                 x1, ns, pos = K.tome_merge_fwd(x1, s0, t, r, unm, src, dst, size_in=sizes.get(si))
                 new_size[si] = ns
+                track(si, t, r, pos)
                 tome_sets.append((s0, t, r, pos, sizes.get(si), ns, unm, src, dst, si))
         elif ctx.r > 0:
             main.wait_stream(side)
@@ -383,6 +396,7 @@ class Encoder1DBlock(Bindable):
             else:
                 x1, new_size, pos = K.tome_merge_fwd(x1, s0, t, ctx.r, unm, src, dst, size_in=size)
             tome = (s0, t, ctx.r, pos, size, new_size, unm, src, dst, plan[0][0])
+            track(plan[0][0], t, ctx.r, pos)
             tome_sets = [tome]
         L2 = x1.shape[1]
         y1, mu1, rs1 = ln1_done if ln1_done is not None else self.ln1.fwd(x1)
@@ -590,12 +604,26 @@ class StackedEncoder1DBlock(Bindable):
         return _StackFn.apply(x.float().contiguous(), self, ctxs)
 
     def forward(self, x, ctxs: List[LayerCtx]):
+        """Returns (x, saved): one saved dict per block. With LayerCtx.track_source the last one
+        also holds "merge_source": {set index: (source (B, t0) int32, merged length)} for every
+        set the blocks merged, the buffers allocated here, once per forward."""
         saved = []
         size = None
+        sources = final_t = None
+        if any(c.track_source for c in ctxs):
+            sources, final_t = {}, {}
+            for c in ctxs:
+                for si, r in c.tome_sets():
+                    if si not in sources:
+                        sources[si] = torch.empty((x.shape[0], c.sets.lens[si]), dtype=torch.int32,
+                                                  device=x.device)
+                    final_t[si] = c.sets.lens[si] - r
         for blk, ctx in zip(self.blocks, ctxs):
             with phase(f"fwd/block{ctx.layer}"):
-                x, sv, size = blk.forward(x, ctx, size)
+                x, sv, size = blk.forward(x, ctx, size, sources)
             saved.append(sv)
+        if sources is not None and saved:
+            saved[-1]["merge_source"] = {si: (buf, final_t[si]) for si, buf in sources.items()}
         return x, saved
 
     def backward(self, dx, saved, ctxs, lo: int = 0, hi: int | None = None):

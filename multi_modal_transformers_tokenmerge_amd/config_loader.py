@@ -16,7 +16,7 @@ which are not available on the GPU box.
   reads (``attention_blocks.stacked_encoder_1d_block.{num_blocks, encoder_1d_block}``,
   ``octo.py:67,80``). New keys: ``token_compression_sequence`` (ToMe),
   ``token_compression_method`` ("tome" | "prune"), ``proportional_attention`` (ToMe's log-size
-  key bias in attention), ``fp8_matmul``, ``t5_num_layers`` and ``text_tokens``.
+  key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``fp8_matmul``, ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
 ``KeyError`` / ``ValueError`` (Hydra raises on both).
@@ -275,6 +275,7 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     kw["fp8"] = bool(cfg.get("fp8_matmul", False))
     kw["compression"] = str(cfg.get("token_compression_method", "tome"))
     kw["proportional_attention"] = bool(cfg.get("proportional_attention", False))
+    kw["track_merge_source"] = bool(cfg.get("track_merge_source", False))
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

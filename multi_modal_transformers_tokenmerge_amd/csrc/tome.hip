@@ -1382,3 +1382,318 @@ extern "C" int mmt_tome_size_bias(const float* size, int B, int t, int set_start
   MMT_CHECK_LAUNCH("mmt_tome_size_bias");
   return MMT_OK;
 }
+
+// ------------------------------------------------- merge source (ToMe's merge_source) + unmerge
+// source[b, p] = the merged row of its set that original token (patch) p of sample b now belongs
+// to. One mmt_tome_source_step per merge composes the layer's pos_map into it; the CSR inverse
+// (group_start / members, members in ascending patch order) turns the unmerge's backward into a
+// segmented sum with a fixed order. Every caller-supplied index is range-checked
+// (checked_index, common.h): an invalid one is replaced by 0 and recorded, never followed.
+namespace {
+
+// The pos_map of tome_merge_fwd_kernel's phase 1 without the rows: the same maps
+// (load_merge_maps), the same row placement (merged_row_source), the same writes.
+constexpr int POSMAP_NT = 256;
+__global__ __launch_bounds__(POSMAP_NT) void tome_pos_map_kernel(
+    const int32_t* __restrict__ unm_g, const int32_t* __restrict__ src_g,
+    const int32_t* __restrict__ dst_g, int t, int r, int flags, int32_t* __restrict__ pos_map,
+    unsigned int* fault) {
+  __shared__ int32_t s_unm[1024];
+  __shared__ int32_t s_src[512];
+  __shared__ int32_t s_dst[512];
+  __shared__ uint32_t s_seen[kSeenWords];
+  const int n = blockIdx.x;
+  const int ta = (t + 1) / 2;
+  const bool dis = flags & MMT_TOME_DISTILL_TOKEN;
+  const bool scatter = !(flags & MMT_TOME_NO_SCATTER);
+  load_merge_maps(n, t, r, unm_g, src_g, dst_g, s_unm, s_src, s_dst, s_seen, fault);
+  int32_t* pm = pos_map + (int64_t)n * t;
+  for (int q = threadIdx.x; q < t - r; q += POSMAP_NT) {
+    int tok, j;
+    merged_row_source(q, ta, r, dis, s_unm, &tok, &j);
+    pm[tok] = q;
+    if (j >= 0 && scatter)
+      for (int i = 0; i < r; ++i)
+        if (s_dst[i] == j) pm[2 * s_src[i]] = q;
+  }
+}
+
+constexpr int SRCSTEP_NT = 256;
+__global__ __launch_bounds__(SRCSTEP_NT) void tome_source_step_kernel(
+    const int32_t* __restrict__ pos_map, int t, int r, int32_t* __restrict__ source, int t0,
+    int first, unsigned int* fault) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * SRCSTEP_NT + threadIdx.x;
+  if (p >= t0) return;
+  const int32_t* pm = pos_map + (int64_t)b * t;
+  int32_t* sp = source + (int64_t)b * t0 + p;
+  const int s = first ? p : checked_index(*sp, t, fault, MMT_FAULT_ROW_INDEX);
+  *sp = checked_index(pm[s], t - r, fault, MMT_FAULT_POS_MAP);
+}
+
+// CSR inverse of one sample's map, one workgroup per sample: histogram (integer LDS atomics: a
+// count does not depend on their order), exclusive scan, then every patch's rank inside its
+// group = the number of lower patches with the same value, so members are in ascending patch
+// order whatever the scheduling.
+constexpr int GROUPS_NT = 1024, GROUPS_MAX = 2048;
+__global__ __launch_bounds__(GROUPS_NT) void tome_source_groups_kernel(
+    const int32_t* __restrict__ source, int t0, int tf, int32_t* __restrict__ group_start,
+    int32_t* __restrict__ members, unsigned int* fault) {
+  __shared__ __attribute__((aligned(16))) int32_t s_val[GROUPS_MAX];
+  __shared__ int32_t s_cnt[GROUPS_MAX];
+  __shared__ int32_t s_wave[GROUPS_NT / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  for (int j = tid; j < GROUPS_MAX; j += GROUPS_NT) {
+    s_cnt[j] = 0;
+    s_val[j] = -1;  // past t0: matches no group
+  }
+  __syncthreads();
+  for (int p = tid; p < t0; p += GROUPS_NT) {
+    const int v = checked_index(source[(int64_t)b * t0 + p], tf, fault, MMT_FAULT_ROW_INDEX);
+    s_val[p] = v;
+    atomicAdd(&s_cnt[v], 1);
+  }
+  __syncthreads();
+  // exclusive scan of s_cnt[0, 2048): two entries per thread, wave scan, wave totals
+  const int c0 = s_cnt[2 * tid], c1 = s_cnt[2 * tid + 1];
+  const int lane = tid & 63, wave = tid >> 6;
+  int inc = c0 + c1;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += up;
+  }
+  if (lane == 63) s_wave[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += s_wave[w];
+  const int ex = base + inc - (c0 + c1);
+  __syncthreads();  // every count is read before its slot becomes a start
+  s_cnt[2 * tid] = ex;
+  s_cnt[2 * tid + 1] = ex + c0;
+  __syncthreads();
+  int32_t* gs = group_start + (int64_t)b * (tf + 1);
+  for (int j = tid; j <= tf; j += GROUPS_NT) gs[j] = j < tf ? s_cnt[j] : t0;
+  int32_t* mb = members + (int64_t)b * t0;
+  for (int p = tid; p < t0; p += GROUPS_NT) {
+    const int v = s_val[p];
+    int rank = 0;
+    for (int p4 = 0; p4 < p; p4 += 4) {
+      const int4 w = *reinterpret_cast<const int4*>(s_val + p4);
+      rank += (w.x == v);
+      rank += (w.y == v) && (p4 + 1 < p);
+      rank += (w.z == v) && (p4 + 2 < p);
+      rank += (w.w == v) && (p4 + 3 < p);
+    }
+    mb[s_cnt[v] + rank] = p;
+  }
+}
+
+// Unmerge forward: a row gather over 16-B chunks (both dtypes move as raw bytes), one block =
+// kMergeRows output rows of one sample, (row, chunk) items streamed with 4 loads in flight per
+// thread as tome_merge_fwd_kernel does. Strides in bytes.
+__global__ __launch_bounds__(256) void tome_unmerge_fwd_kernel(
+    const char* __restrict__ x, int Lout, int nchunk, int64_t xs_n, int64_t xs_t, int set_start,
+    int tf, const int32_t* __restrict__ source, int t0, char* __restrict__ out, int64_t os_n,
+    int64_t os_t, unsigned int* fault) {
+  __shared__ int32_t m_row[kMergeRows];
+  const int n = blockIdx.x;
+  const int row0 = blockIdx.y * kMergeRows;
+  const int nrows = min(kMergeRows, Lout - row0);
+  if (threadIdx.x < nrows) {
+    const int o = row0 + threadIdx.x;
+    int src;
+    if (o < set_start) src = o;
+    else if (o >= set_start + t0) src = o - t0 + tf;
+    else src = set_start + checked_index(source[(int64_t)n * t0 + (o - set_start)], tf, fault,
+                                         MMT_FAULT_ROW_INDEX);
+    m_row[threadIdx.x] = src;
+  }
+  __syncthreads();
+  const char* xb = x + (int64_t)n * xs_n;
+  char* ob = out + (int64_t)n * os_n;
+  const int total = nrows * nchunk;
+  constexpr int G = 4;
+  for (int base = 0; base < total; base += G * 256) {
+    uint4 v[G];
+    int ri[G], ch[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {  // clamped (always valid) addresses: loads issue unconditionally
+      const int idx = min(base + u * 256 + (int)threadIdx.x, total - 1);
+      ri[u] = idx / nchunk;
+      ch[u] = idx - ri[u] * nchunk;
+      v[u] = *reinterpret_cast<const uint4*>(xb + (int64_t)m_row[ri[u]] * xs_t + (int64_t)ch[u] * 16);
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (base + u * 256 + (int)threadIdx.x >= total) break;
+      *reinterpret_cast<uint4*>(ob + (int64_t)(row0 + ri[u]) * os_t + (int64_t)ch[u] * 16) = v[u];
+    }
+  }
+}
+
+// Unmerge backward, the adjoint: copied rows copied, set row j = the fp32 sum of its group's
+// gradient rows in ascending patch order (the order of `members`), starting from 0, rounded once
+// at the store. No atomics. One block = kMergeRows g_x rows of one sample; a group's rows are
+// loaded 4 at a time (all issued before the first add).
+template <typename T>
+__global__ __launch_bounds__(256) void tome_unmerge_bwd_kernel(
+    const T* __restrict__ g, int L, int D, int64_t gs_n, int64_t gs_t, int set_start, int tf,
+    const int32_t* __restrict__ group_start, const int32_t* __restrict__ members, int t0,
+    T* __restrict__ gx, int64_t xs_n, int64_t xs_t, unsigned int* fault) {
+  __shared__ int32_t m_beg[kMergeRows], m_end[kMergeRows];  // m_end < 0: copy of row m_beg
+  const int n = blockIdx.x;
+  const int row0 = blockIdx.y * kMergeRows;
+  const int nrows = min(kMergeRows, L - row0);
+  if (threadIdx.x < nrows) {
+    const int row = row0 + threadIdx.x;
+    if (row < set_start || row >= set_start + tf) {
+      m_beg[threadIdx.x] = row < set_start ? row : row - tf + t0;
+      m_end[threadIdx.x] = -1;
+    } else {
+      const int32_t* gsb = group_start + (int64_t)n * (tf + 1) + (row - set_start);
+      int beg = gsb[0], end = gsb[1];
+      if (beg < 0 || end > t0 || beg > end) {  // not a CSR row of [0, t0): an empty group
+        record_fault(fault, MMT_FAULT_ROW_INDEX);
+        beg = end = 0;
+      }
+      m_beg[threadIdx.x] = beg;
+      m_end[threadIdx.x] = end;
+    }
+  }
+  __syncthreads();
+  constexpr int V = Vec<T>::N;
+  const int nchunk = D / V;
+  const T* gb = g + (int64_t)n * gs_n;
+  T* xb = gx + (int64_t)n * xs_n;
+  const int32_t* mb = members + (int64_t)n * t0;
+  const int total = nrows * nchunk;
+  for (int idx = threadIdx.x; idx < total; idx += 256) {
+    const int ri = idx / nchunk, ch = idx - ri * nchunk;
+    T* dst = xb + (int64_t)(row0 + ri) * xs_t + ch * V;
+    const int beg = m_beg[ri], end = m_end[ri];
+    if (end < 0) {  // copy row, as raw bytes
+      *reinterpret_cast<uint4*>(dst) =
+          *reinterpret_cast<const uint4*>(gb + (int64_t)beg * gs_t + ch * V);
+      continue;
+    }
+    float acc[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    for (int k = beg; k < end; k += 4) {
+      float w[4][V];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {  // clamped addresses: the 4 loads issue together
+        const int p = checked_index(mb[min(k + u, end - 1)], t0, fault, MMT_FAULT_ROW_INDEX);
+        Vec<T>::load(gb + (int64_t)(set_start + p) * gs_t + ch * V, w[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (k + u < end)
+#pragma unroll
+          for (int e = 0; e < V; ++e) acc[e] = acc[e] + w[u][e];
+    }
+    Vec<T>::store(dst, acc);
+  }
+}
+
+}  // namespace
+
+extern "C" int mmt_tome_pos_map(const int32_t* unm_idx, const int32_t* src_idx,
+                                const int32_t* dst_idx, int n, int t, int r, int flags,
+                                int32_t* pos_map, mmt_stream_t stream) {
+  MMT_CHECK_ARG((unm_idx || (t + 1) / 2 == r) && src_idx && dst_idx && pos_map,
+                "mmt_tome_pos_map: null pointer");  // unm may be NULL when every A token merges
+  MMT_CHECK_ARG(n > 0 && t >= 2, "mmt_tome_pos_map: bad shape n=%d t=%d", n, t);
+  MMT_CHECK_ARG(r > 0 && r <= t / 2 && (t + 1) / 2 - r <= 1024 && r <= 512,
+                "mmt_tome_pos_map: bad r=%d for t=%d", r, t);
+  MMT_CHECK_ARG(!(flags & MMT_TOME_DISTILL_TOKEN) || (t + 1) / 2 - r >= 1,
+                "mmt_tome_pos_map: the distill layout needs an unmerged a token (r=%d, t=%d)", r, t);
+  hipLaunchKernelGGL(tome_pos_map_kernel, dim3(n), dim3(POSMAP_NT), 0, as_stream(stream), unm_idx,
+                     src_idx, dst_idx, t, r, flags, pos_map, fault_word());
+  MMT_CHECK_LAUNCH("mmt_tome_pos_map");
+  return MMT_OK;
+}
+
+extern "C" int mmt_tome_source_step(const int32_t* pos_map, int n, int t, int r, int32_t* source,
+                                    int t0, int first, mmt_stream_t stream) {
+  MMT_CHECK_ARG(pos_map && source, "mmt_tome_source_step: null pointer");
+  MMT_CHECK_ARG(n > 0 && t >= 2 && t0 >= t && t0 <= 2048,
+                "mmt_tome_source_step: bad shape n=%d t=%d t0=%d (t <= t0 <= 2048)", n, t, t0);
+  MMT_CHECK_ARG(r > 0 && r <= t / 2, "mmt_tome_source_step: bad r=%d for t=%d", r, t);
+  MMT_CHECK_ARG(!first || t0 == t, "mmt_tome_source_step: first needs t0 == t (t0=%d, t=%d)", t0, t);
+  hipLaunchKernelGGL(tome_source_step_kernel, dim3((t0 + SRCSTEP_NT - 1) / SRCSTEP_NT, n),
+                     dim3(SRCSTEP_NT), 0, as_stream(stream), pos_map, t, r, source, t0, first,
+                     fault_word());
+  MMT_CHECK_LAUNCH("mmt_tome_source_step");
+  return MMT_OK;
+}
+
+extern "C" int mmt_tome_source_groups(const int32_t* source, int n, int t0, int tf,
+                                      int32_t* group_start, int32_t* members, mmt_stream_t stream) {
+  MMT_CHECK_ARG(source && group_start && members, "mmt_tome_source_groups: null pointer");
+  MMT_CHECK_ARG(n > 0 && tf > 0 && tf <= t0 && t0 <= GROUPS_MAX,
+                "mmt_tome_source_groups: bad shape n=%d t0=%d tf=%d (tf <= t0 <= %d)", n, t0, tf,
+                GROUPS_MAX);
+  hipLaunchKernelGGL(tome_source_groups_kernel, dim3(n), dim3(GROUPS_NT), 0, as_stream(stream),
+                     source, t0, tf, group_start, members, fault_word());
+  MMT_CHECK_LAUNCH("mmt_tome_source_groups");
+  return MMT_OK;
+}
+
+static int aligned16(const void* a, const void* b) {
+  return (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0;
+}
+
+extern "C" int mmt_tome_unmerge_fwd(const void* x, int dtype, int n, int L, int D, int64_t x_s_n,
+                                    int64_t x_s_t, int set_start, int tf, const int32_t* source,
+                                    int t0, void* out, int64_t o_s_n, int64_t o_s_t,
+                                    mmt_stream_t stream) {
+  MMT_CHECK_ARG(x && source && out, "mmt_tome_unmerge_fwd: null pointer");
+  MMT_CHECK_ARG(n > 0 && L > 0 && D > 0 && tf > 0 && tf <= t0 && t0 <= 2048,
+                "mmt_tome_unmerge_fwd: bad shape n=%d L=%d D=%d tf=%d t0=%d (tf <= t0 <= 2048)", n,
+                L, D, tf, t0);
+  MMT_CHECK_ARG(set_start >= 0 && set_start + tf <= L,
+                "mmt_tome_unmerge_fwd: the set [%d, %d) leaves the sequence of %d rows", set_start,
+                set_start + tf, L);
+  MMT_CHECK_ARG(dtype == MMT_F32 || dtype == MMT_BF16, "mmt_tome_unmerge_fwd: dtype %d", dtype);
+  MMT_CHECK_ARG(D % 8 == 0 && check_vec(dtype, D, x_s_n, x_s_t, o_s_n, o_s_t) && aligned16(x, out),
+                "mmt_tome_unmerge_fwd: D must be a multiple of 8, strides and bases of 16 bytes");
+  const int es = dtype == MMT_BF16 ? 2 : 4;
+  const int Lout = L - tf + t0;
+  hipLaunchKernelGGL(tome_unmerge_fwd_kernel, dim3(n, (Lout + kMergeRows - 1) / kMergeRows),
+                     dim3(256), 0, as_stream(stream), (const char*)x, Lout, D * es / 16, x_s_n * es,
+                     x_s_t * es, set_start, tf, source, t0, (char*)out, o_s_n * es, o_s_t * es,
+                     fault_word());
+  MMT_CHECK_LAUNCH("mmt_tome_unmerge_fwd");
+  return MMT_OK;
+}
+
+extern "C" int mmt_tome_unmerge_bwd(const void* g, int dtype, int n, int L, int D, int64_t g_s_n,
+                                    int64_t g_s_t, int set_start, int tf,
+                                    const int32_t* group_start, const int32_t* members, int t0,
+                                    void* g_x, int64_t gx_s_n, int64_t gx_s_t, mmt_stream_t stream) {
+  MMT_CHECK_ARG(g && group_start && members && g_x, "mmt_tome_unmerge_bwd: null pointer");
+  MMT_CHECK_ARG(n > 0 && L > 0 && D > 0 && tf > 0 && tf <= t0 && t0 <= 2048,
+                "mmt_tome_unmerge_bwd: bad shape n=%d L=%d D=%d tf=%d t0=%d (tf <= t0 <= 2048)", n,
+                L, D, tf, t0);
+  MMT_CHECK_ARG(set_start >= 0 && set_start + tf <= L,
+                "mmt_tome_unmerge_bwd: the set [%d, %d) leaves the sequence of %d rows", set_start,
+                set_start + tf, L);
+  MMT_CHECK_ARG(dtype == MMT_F32 || dtype == MMT_BF16, "mmt_tome_unmerge_bwd: dtype %d", dtype);
+  MMT_CHECK_ARG(D % 8 == 0 && check_vec(dtype, D, g_s_n, g_s_t, gx_s_n, gx_s_t) && aligned16(g, g_x),
+                "mmt_tome_unmerge_bwd: D must be a multiple of 8, strides and bases of 16 bytes");
+  const dim3 grid(n, (L + kMergeRows - 1) / kMergeRows);
+  hipStream_t s = as_stream(stream);
+  unsigned int* const fault = fault_word();
+  if (dtype == MMT_F32)
+    hipLaunchKernelGGL(tome_unmerge_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)g, L, D,
+                       g_s_n, g_s_t, set_start, tf, group_start, members, t0, (float*)g_x, gx_s_n,
+                       gx_s_t, fault);
+  else
+    hipLaunchKernelGGL(tome_unmerge_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)g, L,
+                       D, g_s_n, g_s_t, set_start, tf, group_start, members, t0, (bf16_t*)g_x,
+                       gx_s_n, gx_s_t, fault);
+  MMT_CHECK_LAUNCH("mmt_tome_unmerge_bwd");
+  return MMT_OK;
+}

@@ -124,6 +124,7 @@ class DDPStep:
         self.loss_buf = torch.zeros(1, device=model.device)
         self.graphs = []
         self._st = {}
+        self._sources = None
 
     # --------------------------------------------------------------- schedule pieces
     def _t5_prime(self):
@@ -220,6 +221,13 @@ class DDPStep:
     def _opt(self):
         self.state.apply_gradients()
 
+    def merge_source(self):
+        """{set index: MergeSource} of the last step (Octo.merge_source; needs
+        OctoConfig.track_merge_source). The source steps are part of the captured forward and
+        write the buffers that capture allocated (kept here), so this reads the last replay's
+        maps; without a graph, the model's last forward."""
+        return self.model.merge_source(_maps=self._sources)
+
     @property
     def exposed_bytes(self) -> int:
         """fp32 gradient bytes all-reduced after the backward's last stage (not overlapped)."""
@@ -308,6 +316,9 @@ class DDPStep:
                 self._fwd_bwd()
                 self._opt()
             cap(whole)
+        # the captured forward's merge-source buffers (None with track_merge_source off): held
+        # here so that an eager forward of the model in between does not hide them
+        self._sources = getattr(self.model, "_merge_sources", None)
         return self
 
     def __call__(self):

@@ -59,10 +59,18 @@ class OctoConfig:
     # votes as the patches it stands for (a per-key bias inside the attention kernels). Needs
     # compression == "tome" (pruning carries no sizes); a no-op without token_compression_sequence
     proportional_attention: bool = False
+    # ToMe merge source (YAML key track_merge_source): every merge also composes its pos_map into
+    # a per-set patch -> merged token map (one small launch per merged set and block, captured
+    # with the step), read back with Octo.merge_source. Needs compression == "tome"; a no-op
+    # without token_compression_sequence
+    track_merge_source: bool = False
 
     def __post_init__(self):
         if self.proportional_attention and self.compression != "tome":
             raise ValueError(f"proportional_attention needs compression='tome' (token sizes), got "
+                             f"{self.compression!r}")
+        if self.track_merge_source and self.compression != "tome":
+            raise ValueError(f"track_merge_source needs compression='tome' (merge maps), got "
                              f"{self.compression!r}")
 
     @property

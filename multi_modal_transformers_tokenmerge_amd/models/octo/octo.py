@@ -40,6 +40,7 @@ from ...schedules import Constant, Schedule, WarmupCosine, WarmupRsqrt
 from ...tokenizers.images.image_tokenizer import ImageTokenizer
 from ...tokenizers.readout.readout import AddPositionEmbedding
 from ...tokenizers.text.t5_base import T5Tokenizer
+from ...tokenizers.token_compression import MergeSource
 from ...tokenizers.token_sequencer import Image, Readout, Text, TokenSequence
 from .config import OctoConfig, get_config
 
@@ -110,6 +111,7 @@ class Octo:
         if os.environ.get("MMT_DETERMINISTIC", "0") == "1" and torch.device(self.device).type == "cuda":
             store.set_deterministic(True)
         self.t5 = T5Tokenizer(cfg.t5).materialize(self.device, seed + 1) if self.has_text else None
+        self._merge_sources = None  # the last tracked forward's source buffers (merge_source)
         self._build_tables()
 
     # ------------------------------------------------------------------ static tables
@@ -192,11 +194,12 @@ class Octo:
 
     def layer_ctxs(self, train: bool, rng, sample_offset: int) -> List[LayerCtx]:
         prop = bool(self.cfg.proportional_attention)
+        track = bool(self.cfg.track_merge_source)
         ctxs, carried = [], -1  # carried: the set whose sizes the last single-set merge handed on
         for i, (s, t, ts, r, pr, plan) in enumerate(self.layer_sets):
             ctxs.append(LayerCtx(layer=i, sets=s, table=t, tome_set=ts, r=r, prune=pr, train=train,
                                  rng=rng, sample_offset=sample_offset, tome_plan=plan,
-                                 prop_attn=prop, size_set=carried))
+                                 prop_attn=prop, size_set=carried, track_source=track))
             if len(plan) == 1:
                 carried = plan[0][0]
         return ctxs
@@ -236,8 +239,31 @@ class Octo:
                 c.tome_forced = idx
         with phase("fwd/blocks"):
             xL, ssv = self.stack.forward(x0, ctxs)
+        if self.cfg.track_merge_source:
+            # the model keeps the forward's source buffers: a captured step drops its saved state,
+            # and every replay rewrites these same buffers
+            self._merge_sources = ssv[-1].get("merge_source") if ssv else {}
         st.update(ctxs=ctxs, stack_sv=ssv, NI=NI, T=T)
         return xL, st
+
+    def merge_source(self, st: Optional[Dict] = None, *, _maps=None) -> Dict[int, MergeSource]:
+        """{set index: MergeSource} of the forward that produced the saved state ``st``: for every
+        merged token set, which of its final rows each original token (image patch) ended up in.
+        ``st`` None: the model's last forward (a captured step holds its own buffers, which every
+        replay rewrites: DDPStep.merge_source). The maps are copies: a later forward or replay does
+        not change them. Needs OctoConfig.track_merge_source."""
+        if not self.cfg.track_merge_source:
+            raise RuntimeError("merge_source: this model was built with track_merge_source off "
+                               "(OctoConfig.track_merge_source / YAML track_merge_source: true)")
+        if _maps is not None:
+            maps = _maps
+        elif st is None:
+            maps = self._merge_sources
+        else:
+            maps = st["stack_sv"][-1].get("merge_source") if st.get("stack_sv") else None
+        if maps is None:
+            raise RuntimeError("merge_source: no tracked forward has run yet")
+        return {si: MergeSource(buf.clone(), t) for si, (buf, t) in sorted(maps.items())}
 
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
                                        sample_offset=0, inject: Optional[dict] = None, t5_out=None):

@@ -7,6 +7,10 @@
 * ``merge(x, mode="sum")`` (:90-109) runs the fused gather/scatter kernel (plain sum).
 * ``merge_wavg(merge, x, size)`` (:114-129) is ONE fused kernel (weighted sum + division) with an
   autograd backward (a weighted gather kernel).
+* ``merge_source(merge, source=None)`` is ToMe's merge source in index form (``MergeSource``: for
+  every original token the merged token that stands for it, with a lazily built CSR inverse), and
+  ``unmerge(x, source, set_start=0)`` spreads merged rows back over the original tokens (a row
+  gather; its backward a fixed-order segmented sum). The reference has neither.
 
 All indices are int32 device tensors, bit-exact with the canonical oracle (oracle/tome_ref.c).
 """
@@ -94,6 +98,102 @@ def merge_wavg(merge: Callable, x: torch.Tensor,
         return x / size, size
     out, size_out = merge.merge_wavg(x, size)
     return out, size_out[..., None]
+
+
+class MergeSource:
+    """ToMe's merge source in index form: ``source`` (n, t0) int32 names, for every original token
+    (patch) of a set, the row of the current ``t`` merged tokens that stands for it. The CSR
+    inverse (``group_start`` (n, t + 1), ``members`` (n, t0), each group's patches ascending) is
+    built on first use by one kernel; ``source`` must not be written afterwards."""
+
+    def __init__(self, source: torch.Tensor, t: int):
+        if source.dim() != 2 or source.dtype != torch.int32:
+            raise ValueError("source must be an (n, t0) int32 tensor")
+        if not 0 < t <= source.shape[1]:
+            raise ValueError(f"t={t} must be in 1..t0={source.shape[1]}")
+        self.source, self.t = source.contiguous(), int(t)
+        self._groups = None
+
+    @property
+    def n(self) -> int:
+        return self.source.shape[0]
+
+    @property
+    def t0(self) -> int:
+        return self.source.shape[1]
+
+    def groups(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._groups is None:
+            self._groups = K.tome_source_groups(self.source, self.t)
+        return self._groups
+
+    @property
+    def group_start(self) -> torch.Tensor:
+        return self.groups()[0]
+
+    @property
+    def members(self) -> torch.Tensor:
+        return self.groups()[1]
+
+    def counts(self) -> torch.Tensor:
+        """(n, t) int32: how many original tokens each merged token stands for."""
+        gs = self.group_start
+        return gs[:, 1:] - gs[:, :-1]
+
+    def as_matrix(self) -> torch.Tensor:
+        """ToMe's (n, t, t0) 0/1 source matrix (fp32). Small inspection only."""
+        m = torch.zeros((self.n, self.t, self.t0), dtype=torch.float32, device=self.source.device)
+        return m.scatter_(1, self.source.long()[:, None, :], 1.0)
+
+
+def merge_source(merge: Callable, source: MergeSource | None = None, *,
+                 shape: Tuple[int, int] | None = None, device=None) -> MergeSource:
+    """ToMe's ``merge_source(merge, x, source)`` without the unused x: the source after applying
+    ``merge`` (a TokenMerge), starting from the identity when ``source`` is None. The do_nothing
+    closure returns ``source`` unchanged, or the identity map of ``shape`` = (n, t) on ``device``
+    (it carries no shape of its own). The given source is left as it is."""
+    if not isinstance(merge, TokenMerge):
+        if source is not None:
+            return source
+        if shape is None:
+            raise ValueError("merge_source(do_nothing) from the identity needs shape=(n, t)")
+        n, t = shape
+        ident = torch.arange(t, dtype=torch.int32, device=device or "cuda").repeat(n, 1)
+        return MergeSource(ident, t)
+    pos_map = K.tome_pos_map(merge.unm_idx, merge.src_idx, merge.dst_idx, merge.t, merge.r,
+                             merge.flags)
+    if source is None:
+        buf = torch.empty_like(pos_map)
+        K.tome_source_step(pos_map, merge.r, buf, first=True)
+    else:
+        if source.t != merge.t:
+            raise ValueError(f"the source holds {source.t} merged tokens, the merge takes {merge.t}")
+        buf = K.tome_source_step(pos_map, merge.r, source.source.clone())
+    return MergeSource(buf, merge.t - merge.r)
+
+
+class _UnmergeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, src, set_start):
+        ctx.src, ctx.set_start = src, set_start
+        return K.tome_unmerge_fwd(x, set_start, src.t, src.source)
+
+    @staticmethod
+    def backward(ctx, g):
+        gs, members = ctx.src.groups()
+        if g.stride(2) != 1 or g.stride(1) != g.shape[2]:
+            g = g.contiguous()
+        return K.tome_unmerge_bwd(g, ctx.set_start, ctx.src.t, gs, members), None, None
+
+
+def unmerge(x: torch.Tensor, source: MergeSource, set_start: int = 0) -> torch.Tensor:
+    """Spread merged tokens back over the original ones: x (n, L, D) holds ``source.t`` merged
+    rows at [set_start, set_start + t); the result (n, L - t + t0, D) holds, at set_start + p, the
+    merged row of original token p, the other rows copied. Differentiable with respect to x (the
+    backward sums each group's gradient rows in ascending patch order, bitwise reproducible)."""
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    return _UnmergeFn.apply(x, source, set_start)
 
 
 class _TopKFn(torch.autograd.Function):
