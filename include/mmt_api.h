@@ -559,6 +559,48 @@ int mmt_rows_mean_fwd(const void* x, int64_t xs_b, int64_t xs_t, int B, int D,
 int mmt_rows_mean_bwd(const void* de, int64_t ld_de, int B, int L, int D, const int32_t* row_flag,
                       int nrows, void* dx, mmt_stream_t stream);
 
+/* ------------------------------------------------------------------ attention pooling
+ * MultiHeadAttentionPooling (attention_blocks/attention.py:122-150) of the readout tokens, the
+ * pieces around its GEMMs (csrc/pool.hip). None of them accumulates across workgroups (no
+ * atomics): batch reductions are per-sample arrays for mmt_colsum.
+ *
+ * Readout gather: r (B, n, D) bf16 contiguous = x[b, rows[i], :] (x fp32, element strides xs_b,
+ * xs_t multiples of 4, 16-B aligned; D % 8 == 0). rows outside [0, L): MMT_FAULT_ROW_INDEX. */
+int mmt_rows_gather_bf16(const void* x, int64_t xs_b, int64_t xs_t, int B, int L, int D,
+                         const int32_t* rows, int n, void* r, mmt_stream_t stream);
+/* backward, mmt_rows_mean_bwd's contract: writes the whole contiguous fp32 dx (B, L, D):
+ * dr[b, row_flag[l], :] (dr bf16 (B, n, D) contiguous) where row_flag[l] >= 0, 0 in every other
+ * row. row_flag[l] >= n: MMT_FAULT_ROW_INDEX. */
+int mmt_rows_scatter_bwd(const void* dr, int B, int L, int D, const int32_t* row_flag, int n,
+                         void* dx, mmt_stream_t stream);
+/* Single-query multi-head attention core. q (H * Dh) fp32: the projected, scaled query, shared by
+ * the batch; k, v bf16, row (b, j) at (b * n + j) * ld_kv (both may be halves of one (B n, 2 D)
+ * GEMM output); p (B, H, n) fp32 = softmax_j(q_h . k_bjh) (fp32 scores, max-subtracted), saved for
+ * the backward; ctx (B, H * Dh) bf16, row stride ld_ctx, = sum_j p v accumulated in fp32.
+ * 1 <= n <= 64, Dh % 8 == 0, Dh <= 512, strides multiples of 8, 16-B aligned bases. */
+int mmt_attn_pool_fwd(const float* q, const void* k, const void* v, int64_t ld_kv, int B, int n,
+                      int H, int Dh, void* ctx, int64_t ld_ctx, float* p, mmt_stream_t stream);
+/* backward: dctx (B, H * Dh) bf16, row stride ld_dctx. dv[b,j,h,:] = p[b,h,j] dctx[b,h,:] and
+ * dk[b,j,h,:] = ds[b,h,j] q[h,:] (bf16, row stride ld_dkv), ds = p (dp - sum_j p dp), dp[b,h,j] =
+ * dctx[b,h,:] . v[b,j,h,:]; dqb (B, H * Dh) fp32 contiguous = sum_j ds[b,h,j] k[b,j,h,:], the
+ * per-sample query gradient (d(q) = its column sum). */
+int mmt_attn_pool_bwd(const void* dctx, int64_t ld_dctx, const float* p, const float* q,
+                      const void* k, const void* v, int64_t ld_kv, int B, int n, int H, int Dh,
+                      void* dk, void* dv, int64_t ld_dkv, float* dqb, mmt_stream_t stream);
+/* flax.linen.LayerNorm over the FEATURE axis (reduction_axes [-1]) of (B, D) rows: fast variance
+ * max(0, E[x^2] - E[x]^2), y = (x - mean) (rsqrt(var + eps) gamma) + beta. x fp32 or bf16
+ * (x_dtype), row stride ldx; y bf16, row stride ldy; mean, rstd fp32 (B). D % 8 == 0. */
+int mmt_layernorm_fwd(const void* x, int x_dtype, int64_t ldx, int B, int D, const float* gamma,
+                      const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd,
+                      mmt_stream_t stream);
+/* dx = LN backward (+ addend, which may alias dx); x, addend and dx have x_dtype, dy has dy_dtype
+ * (as mmt_seqnorm_bwd). dyxhat (B, D) fp32 contiguous = dy xhat per row: d(scale) is its column
+ * sum and d(bias) the column sum of dy (mmt_colsum). */
+int mmt_layernorm_bwd(const void* dy, int dy_dtype, int64_t ld_dy, const void* x, int x_dtype,
+                      int64_t ldx, int B, int D, const float* mean, const float* rstd,
+                      const float* gamma, const void* addend, int64_t ld_add, void* dx,
+                      int64_t ld_dx, float* dyxhat, mmt_stream_t stream);
+
 /* ------------------------------------------------------------------ diffusion head
  * DiffusionActionHead.denoise_loss (diffusion.py:110-143) pieces: t ~ U{0..steps-1}, eps ~ N(0,1)
  * (or injected), noisy = sqrt(abar_t) a + sqrt(1-abar_t) eps written to cat[:, :A] (bf16),

@@ -88,6 +88,12 @@ SIGNATURES: dict[str, list] = {
     "mmt_add_position_embedding": [P, P, P, I, I, I, P],
     "mmt_rows_mean_fwd": [P, L, L, I, I, P, I, P, L, P],
     "mmt_rows_mean_bwd": [P, L, I, I, I, P, I, P, P],
+    "mmt_rows_gather_bf16": [P, L, L, I, I, I, P, I, P, P],
+    "mmt_rows_scatter_bwd": [P, I, I, I, P, I, P, P],
+    "mmt_attn_pool_fwd": [P, P, P, L, I, I, I, I, P, L, P, P],
+    "mmt_attn_pool_bwd": [P, L, P, P, P, P, L, I, I, I, I, P, P, L, P, P],
+    "mmt_layernorm_fwd": [P, I, L, I, I, P, P, F, P, L, P, P, P],
+    "mmt_layernorm_bwd": [P, I, L, P, I, L, I, I, P, P, P, P, L, P, L, P, P],
     "mmt_diffusion_prep": [P, I, I, I, L, P, P, P, I, P, P, P, P, P, L, P, P],
     "mmt_fourier_bwd": [P, I, I, P, P, P, P],
     "mmt_diffusion_loss": [P, L, P, I, I, F, P, P, P],

@@ -954,3 +954,131 @@ def embedding_gather(ids: torch.Tensor, table: torch.Tensor, out=None):
 def cast_f32_bf16(a: torch.Tensor, out: torch.Tensor):
     _C.call("mmt_cast_f32_bf16", ptr(a), ptr(out), a.numel(), _C.stream_ptr())
     return out
+
+
+# ---------------------------------------------------------------------- attention pooling
+def _rows2d(t: torch.Tensor, D: int, what: str, dtypes=(torch.bfloat16,)):
+    if t.dim() != 2 or t.shape[1] != D or t.dtype not in dtypes or t.stride(1) != 1:
+        raise ValueError(f"{what} must be {dtypes} (rows, {D}) with unit inner stride")
+
+
+def rows_gather_bf16(x: torch.Tensor, rows: torch.Tensor, out: torch.Tensor | None = None):
+    """x (B, L, D) fp32 (strided, unit inner stride), rows (n,) int32 -> (B, n, D) bf16."""
+    _dev(x, rows, out)
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError("x must be fp32 (B, L, D) with unit inner stride")
+    B, L, D = x.shape
+    n = rows.numel()
+    _check_i32(rows, (n,), "rows")
+    if out is None:
+        out = torch.empty((B, n, D), dtype=torch.bfloat16, device=x.device)
+    if tuple(out.shape) != (B, n, D) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous bf16 {(B, n, D)}")
+    _C.call("mmt_rows_gather_bf16", ptr(x), x.stride(0), x.stride(1), B, L, D, ptr(rows), n,
+            ptr(out), _C.stream_ptr())
+    return out
+
+
+def rows_scatter_bwd(dr: torch.Tensor, row_flag: torch.Tensor, out: torch.Tensor | None = None):
+    """dr (B, n, D) bf16 contiguous, row_flag (L,) int32 (slot index or -1) -> the whole fp32
+    (B, L, D) gradient: dr[b, row_flag[l]] in the flagged rows, 0 elsewhere."""
+    _dev(dr, row_flag, out)
+    if dr.dim() != 3 or dr.dtype != torch.bfloat16 or not dr.is_contiguous():
+        raise ValueError("dr must be contiguous bf16 (B, n, D)")
+    B, n, D = dr.shape
+    L = row_flag.numel()
+    _check_i32(row_flag, (L,), "row_flag")
+    if out is None:
+        out = torch.empty((B, L, D), dtype=torch.float32, device=dr.device)
+    if tuple(out.shape) != (B, L, D) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 {(B, L, D)}")
+    _C.call("mmt_rows_scatter_bwd", ptr(dr), B, L, D, ptr(row_flag), n, ptr(out), _C.stream_ptr())
+    return out
+
+
+def _check_pool_kv(q, k, v, B, n, H, Dh):
+    D = H * Dh
+    if q.dtype != torch.float32 or q.numel() != D or not q.is_contiguous():
+        raise ValueError(f"q must be contiguous fp32 ({D},)")
+    _rows2d(k, D, "k")
+    _rows2d(v, D, "v")
+    if k.shape[0] != B * n or v.shape[0] != B * n or k.stride(0) != v.stride(0):
+        raise ValueError(f"k and v must hold {B * n} rows with one row stride")
+
+
+def attn_pool_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, n: int, H: int,
+                  ctx: torch.Tensor | None = None):
+    """Single-query attention: q (H*Dh,) fp32 (projected, scaled), k / v (B*n, H*Dh) bf16 rows
+    (one shared row stride) -> ctx (B, H*Dh) bf16, p (B, H, n) fp32."""
+    _dev(q, k, v, ctx)
+    D = q.numel()
+    Dh = D // max(H, 1)
+    _check_pool_kv(q, k, v, B, n, H, Dh)
+    if ctx is None:
+        ctx = torch.empty((B, D), dtype=torch.bfloat16, device=k.device)
+    _rows2d(ctx, D, "ctx")
+    p = torch.empty((B, H, n), dtype=torch.float32, device=k.device)
+    _C.call("mmt_attn_pool_fwd", ptr(q), ptr(k), ptr(v), k.stride(0), B, n, H, Dh, ptr(ctx),
+            ctx.stride(0), ptr(p), _C.stream_ptr())
+    return ctx, p
+
+
+def attn_pool_bwd(dctx: torch.Tensor, p: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
+                  v: torch.Tensor, dk: torch.Tensor | None = None, dv: torch.Tensor | None = None):
+    """-> dk, dv (B*n, H*Dh) bf16 (halves of one (B*n, 2 H*Dh) buffer unless given), dqb (B, H*Dh)
+    fp32: the per-sample query gradient."""
+    _dev(dctx, p, q, k, v, dk, dv)
+    B, H, n = p.shape
+    D = q.numel()
+    Dh = D // H
+    _check_pool_kv(q, k, v, B, n, H, Dh)
+    _rows2d(dctx, D, "dctx")
+    if p.dtype != torch.float32 or not p.is_contiguous() or dctx.shape[0] != B:
+        raise ValueError("p must be contiguous fp32 (B, H, n) and dctx hold B rows")
+    if dk is None or dv is None:
+        dkv = torch.empty((B * n, 2 * D), dtype=torch.bfloat16, device=k.device)
+        dk, dv = dkv[:, :D], dkv[:, D:]
+    _rows2d(dk, D, "dk")
+    _rows2d(dv, D, "dv")
+    if dk.shape[0] != B * n or dv.shape[0] != B * n or dk.stride(0) != dv.stride(0):
+        raise ValueError(f"dk and dv must hold {B * n} rows with one row stride")
+    dqb = torch.empty((B, D), dtype=torch.float32, device=k.device)
+    _C.call("mmt_attn_pool_bwd", ptr(dctx), dctx.stride(0), ptr(p), ptr(q), ptr(k), ptr(v),
+            k.stride(0), B, n, H, Dh, ptr(dk), ptr(dv), dk.stride(0), ptr(dqb), _C.stream_ptr())
+    return dk, dv, dqb
+
+
+def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                  out: torch.Tensor | None = None):
+    """Feature-axis LayerNorm of x (B, D) bf16 or fp32 rows -> y bf16, mean, rstd (B,) fp32."""
+    _dev(x, gamma, beta, out)
+    B, D = x.shape
+    _rows2d(x, D, "x", (torch.float32, torch.bfloat16))
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.bfloat16, device=x.device)
+    _rows2d(out, D, "out")
+    mean = torch.empty(B, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(B, dtype=torch.float32, device=x.device)
+    _C.call("mmt_layernorm_fwd", ptr(x), _dtype_code(x), x.stride(0), B, D, ptr(gamma), ptr(beta),
+            eps, ptr(out), out.stride(0), ptr(mean), ptr(rstd), _C.stream_ptr())
+    return out, mean, rstd
+
+
+def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean, rstd, gamma, addend=None, out=None):
+    """-> dx (dtype of x; + addend, dtype of x), dyxhat (B, D) fp32 (dy * xhat per row)."""
+    _dev(dy, x, mean, rstd, gamma, addend, out)
+    B, D = x.shape
+    both = (torch.float32, torch.bfloat16)
+    _rows2d(x, D, "x", both)
+    _rows2d(dy, D, "dy", both)
+    if addend is not None:
+        _rows2d(addend, D, "addend", (x.dtype,))
+    if out is None:
+        out = torch.empty((B, D), dtype=x.dtype, device=x.device)
+    _rows2d(out, D, "out", (x.dtype,))
+    dyxhat = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    _C.call("mmt_layernorm_bwd", ptr(dy), _dtype_code(dy), dy.stride(0), ptr(x), _dtype_code(x),
+            x.stride(0), B, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(addend),
+            addend.stride(0) if addend is not None else 0, ptr(out), out.stride(0), ptr(dyxhat),
+            _C.stream_ptr())
+    return out, dyxhat

@@ -37,6 +37,18 @@ def cosine_beta_schedule(timesteps: int, s: float = 0.008) -> np.ndarray:
     return np.clip(betas, 0, 0.999).astype(np.float32)
 
 
+def _pooling_module(node):
+    """The attention_pooling config node (a raw ``_target_`` dict, its LayerSpec, or a built
+    module) as a MultiHeadAttentionPooling."""
+    from ..attention_blocks.attention import MultiHeadAttentionPooling
+    node = spec(node)
+    if isinstance(node, MultiHeadAttentionPooling):
+        return node
+    kw = node.kwargs if hasattr(node, "kwargs") else {k: v for k, v in dict(node).items()
+                                                       if not k.startswith("_")}
+    return MultiHeadAttentionPooling(**kw)
+
+
 def alpha_hats_of(betas: np.ndarray) -> np.ndarray:
     """Reference :84-86: prod(alphas[:i+1]) for each i (float32)."""
     alphas = (1 - betas).astype(np.float32)
@@ -48,18 +60,31 @@ class DiffusionActionHead(Bindable):
     """Reference :68-209: ``DiffusionActionHead(diffusion_steps, attention_pooling,
     denoising_model, rng_collection="diffusion")`` with the model_configs/action_heads/diffusion.yaml
     nodes: ``denoising_model`` = OctoDenoise(time_encoder = FourierFeatures(output_dim, kernel_init,
-    mlp_block), num_blocks, mlp_block) (:30-65). ``attention_pooling`` is accepted and unused, as in
-    the reference (the pooling call is commented out, :99-102: the readouts are averaged).
+    mlp_block), num_blocks, mlp_block) (:30-65). ``readout_pooling="mean"`` (the default):
+    ``attention_pooling`` is accepted and unused, as in the reference (the pooling call is
+    commented out, :99-102: the readouts are averaged). ``readout_pooling="attention"`` builds the
+    MultiHeadAttentionPooling module (attention_blocks/attention.py) from that node and pools the
+    readouts through it, the call the reference left commented out (:99); its parameters are
+    declared after the denoiser's, and its backward is the module's own ``backward`` (the model
+    calls it with what ``loss_backward`` returns).
     ``denoise_loss(readouts, actions)``, ``predict_denoise_term(readouts, time, noisy_actions)`` and
     ``predict_action(readouts)`` take the readout tokens (B, n, D) like the reference; the Octo
     training path feeds the readout MEAN straight from the backbone's fused rows-mean kernel
     (``loss_forward`` / ``*_mean``)."""
 
     def __init__(self, diffusion_steps: int = 32, attention_pooling=None, denoising_model=None,
-                 rng_collection: str = "diffusion"):
+                 rng_collection: str = "diffusion", *, readout_pooling: str = "mean"):
         self.steps = int(diffusion_steps)
         self.rng_collection = rng_collection
         self.attention_pooling = attention_pooling
+        if readout_pooling not in ("mean", "attention"):
+            raise ValueError(f"readout_pooling must be 'mean' or 'attention', got {readout_pooling!r}")
+        self.readout_pooling = readout_pooling
+        self.pooling = None
+        if readout_pooling == "attention":
+            if attention_pooling is None:
+                raise ValueError("readout_pooling='attention' needs the attention_pooling node")
+            self.pooling = _pooling_module(attention_pooling)
         dm = spec(denoising_model)
         te = spec(sget(dm, "time_encoder"))
         self.num_blocks = int(sget(dm, "num_blocks", 1))
@@ -122,15 +147,31 @@ class DiffusionActionHead(Bindable):
                       for i in range(1, self.num_blocks)]
         if self.extra and self.A % 8:
             raise ValueError("OctoDenoise num_blocks > 1 needs action_dim % 8 == 0 (16-B rows)")
+        if self.pooling is not None and not self.pooling.bound:
+            # after the denoiser: the offsets of everything above do not depend on the option (the
+            # Octo model binds its module itself, after every head: attach_pooling)
+            self.pooling.bind(store, f"{name}/MultiHeadAttentionPooling_0", D)
+
+    def attach_pooling(self, module) -> "DiffusionActionHead":
+        """Pool the readouts through ``module``, a MultiHeadAttentionPooling already bound to the
+        head's store (the Octo model declares it after its last head, so the parameter offsets of
+        a default configuration do not depend on the option)."""
+        if not module.bound or module.D != self.D:
+            raise ValueError(f"attach_pooling: the module must be bound at width {self.D}")
+        self.pooling, self.readout_pooling = module, "attention"
+        return self
 
     # ------------------------------------------------------------- reference-signature methods
     def _mean_into(self, readouts: torch.Tensor, out: torch.Tensor):
-        """mean over the readout axis (:102) of (B, n, D) readouts into a (B, D) bf16 view."""
+        """The readouts (B, n, D) pooled into a (B, D) bf16 view: their mean over the readout axis
+        (:102), or with readout_pooling="attention" the pooling module's output (:99)."""
         if readouts.dim() != 3 or readouts.stride(2) != 1:
             raise ValueError(f"readouts must be (batch, tokens, {self.D}) with unit inner stride")
         B, n, D = readouts.shape
         x = readouts if readouts.dtype == torch.float32 else readouts.float()
         rows = torch.arange(n, dtype=torch.int32, device=readouts.device)
+        if self.pooling is not None:
+            return self.pooling.forward(x, rows, out=out)[0]
         _C.call("mmt_rows_mean_fwd", _C.ptr(x), x.stride(0), x.stride(1), B, D, _C.ptr(rows), n,
                 _C.ptr(out), out.stride(0), _C.stream_ptr())
         return out

@@ -1,6 +1,7 @@
 """Transformer blocks, mirroring the reference's
 ``multi_modal_transformers/attention_blocks/attention.py`` (MLPBlock :20-39, Encoder1DBlock
-:41-69, AddPositionEmbedding :71-85, StackedEncoder1DBlock :87-119) with ToMe inserted the way
+:41-69, AddPositionEmbedding :71-85, StackedEncoder1DBlock :87-119, MultiHeadAttentionPooling
+:122-150) with ToMe inserted the way
 ``tome_attention.py:249-256`` intends (after the attention residual, before the MLP LayerNorm).
 
 Semantics kept from the reference:
@@ -37,7 +38,7 @@ from ..layers import (DROP_ATTN, DROP_ATTN_OUT, DROP_MLP_HIDDEN, DROP_MLP_OUT, D
                       SeqLayerNorm)
 from ..config_loader import LayerSpec
 from ..module_api import Bindable, init_from_spec, merge_param, sget, spec
-from ..params import ParamStore, he_normal, normal
+from ..params import ParamStore, const, he_normal, normal
 from ..tracing import phase
 from ..tokenizers.token_sequencer import LayerSets, sets_from_mask
 
@@ -180,6 +181,188 @@ class MLPBlock(Bindable):
         h = self.dense.fwd(x2.contiguous(), act=K.ACT_RELU, **epi(DROP_MLP_HIDDEN))
         y = self.dense_out.fwd(h, out_mode=K.OUT_F32, **epi(DROP_MLP_OUT))
         return y.view(*lead, y.shape[-1])
+
+
+class MultiHeadAttentionPooling(Bindable):
+    """attention.py:122-150: ``MultiHeadAttentionPooling(query_map_input, dot_product_attention,
+    layer_norm, mlp_block)(x, train=False)``: one learnt query (``learnt_q_input`` (1, 1, D), tiled
+    over the batch) attends to the n tokens of x (B, n, D) through
+    flax.linen.MultiHeadDotProductAttention (query / key / value / out DenseGeneral with bias,
+    q / sqrt(Dh), fp32 softmax, no mask, no dropout), a = attention output (B, 1, D);
+    y = LayerNorm(a); y = MLPBlock(y, train); returns a + y. The diffusion head calls it without
+    ``train`` (diffusion.py:99), so the MLP dropouts stay off, as for the denoiser's MLPBlocks.
+
+    ``layer_norm.reduction_axes`` is honoured: [1], the reference YAML's value
+    (model_configs/action_heads/diffusion.yaml:19-23), normalises over the length-1 pooled sequence
+    (the sequence-axis kernels at L = 1: y = bias, no gradient reaches a through the norm);
+    [-1] normalises over the features (csrc/pool.hip mmt_layernorm_*).
+
+    On the device: readout gather to bf16, ONE key / value GEMM (a fused ``kv`` Dense, split into
+    key / value on export like the blocks' fused QKV), the single-query attention kernel, the
+    out-projection, the LayerNorm and the two MLP GEMMs, the second with the residual a in its
+    epilogue writing the pooled embedding straight into the caller's destination. The query
+    projection of the (1, D) probe is an M = 1 product on the GEMM path (fp32 output), once per
+    step, and so is its dX; the rank-1 d(query kernel), a product of reduction length 1, is one
+    elementwise torch kernel (attention pooling)."""
+
+    def __init__(self, query_map_input=None, dot_product_attention=None, layer_norm=None,
+                 mlp_block=None):
+        self.query_map_input = spec(query_map_input)
+        self.attention = spec(dot_product_attention)
+        self.layer_norm = spec(layer_norm)
+        mlp = spec(mlp_block)
+        if mlp is None:
+            raise ValueError("MultiHeadAttentionPooling needs an mlp_block")
+        if not isinstance(mlp, MLPBlock):
+            raise TypeError(f"mlp_block must be an MLPBlock node, got {type(mlp).__name__}")
+        self.mlp = mlp
+        self.H = int(sget(self.attention, "num_heads", 1))
+        if float(sget(self.attention, "dropout_rate", 0.0)) != 0.0:
+            raise NotImplementedError("MultiHeadAttentionPooling: attention dropout (the reference "
+                                      "config has none and the module is called deterministic)")
+        ra = sget(self.layer_norm, "reduction_axes", [-1])
+        ra = [int(v) for v in (ra if isinstance(ra, (list, tuple)) else [ra])]
+        if ra in ([1], [-2]):
+            self.norm_axis = 1
+        elif ra in ([-1], [2]):
+            self.norm_axis = -1
+        else:
+            raise NotImplementedError(f"LayerNorm reduction_axes {ra}: [1] (the pooled sequence) "
+                                      "or [-1] (the features)")
+        self.eps = float(sget(self.layer_norm, "epsilon", 1e-6))
+
+    @classmethod
+    def create(cls, store: ParamStore, name: str, D: int, num_heads: int, mlp_dim: int | None = None,
+               eps: float = 1e-6, reduction_axes=(-1,)) -> "MultiHeadAttentionPooling":
+        """The module from its dimensions, declared in ``store`` (the Octo model's path)."""
+        he = {"_target_": "flax.linen.initializers.he_normal"}
+        m = cls({"kernel_init": he},
+                LayerSpec("flax.linen.MultiHeadDotProductAttention",
+                          {"num_heads": num_heads, "kernel_init": he}),
+                LayerSpec("flax.linen.LayerNorm", {"epsilon": eps,
+                                                   "reduction_axes": list(reduction_axes),
+                                                   "feature_axes": [-1]}),
+                MLPBlock(LayerSpec("flax.linen.Dense", {"features": mlp_dim or D}),
+                         LayerSpec("flax.linen.relu", partial=True),
+                         LayerSpec("flax.linen.Dropout", {"rate": 0.1}),
+                         LayerSpec("flax.linen.Dense", {"features": D})))
+        return m.bind(store, name, D)
+
+    def _declare(self, store: ParamStore, name: str, D: int):
+        if D % self.H:
+            raise ValueError(f"attention pooling: the width {D} must be divisible by num_heads "
+                             f"{self.H}")
+        self.D, self.Dh = D, D // self.H
+        if self.Dh % 8 or self.Dh > 512:
+            raise ValueError(f"attention pooling: head width {self.Dh} must be a multiple of 8, "
+                             "at most 512 (16-B rows, one wave per key row)")
+        self.scale = self.Dh ** -0.5
+        sa = self.attention
+        qf = sget(sa, "qkv_features")
+        if qf is not None and int(qf) != D:
+            raise ValueError(f"qkv_features {qf} != the input width {D}")
+        kinit = lambda: init_from_spec(sget(sa, "kernel_init"), (D, D))   # noqa: E731
+        binit = lambda: init_from_spec(sget(sa, "bias_init"), (D,), const(0.0))   # noqa: E731
+        self.probe = store.add(f"{name}/learnt_q_input", (1, 1, D),
+                               init_from_spec(sget(self.query_map_input, "kernel_init"), (1, 1, D)))
+        a = f"{name}/MultiHeadDotProductAttention_0"
+        self.query = Dense(store, f"{a}/query", D, D, kernel_init=kinit(), bias_init=binit())
+        self.kv = Dense(store, f"{a}/kv", D, 2 * D, kernel_init=kinit(), bias_init=binit())
+        self.out = Dense(store, f"{a}/out", D, D, kernel_init=kinit(), bias_init=binit())
+        self.ln = SeqLayerNorm(store, f"{name}/LayerNorm_0", D, self.eps)
+        self.mlp.bind(store, f"{name}/MLPBlock_0", D)
+        if self.mlp.dense_out.out_f != D:
+            raise ValueError("mlp_block.dense_out.features must equal the input width (residual)")
+        if self.mlp.dense.fp8 or self.mlp.dense_out.fp8:
+            raise NotImplementedError("attention pooling runs its products in bf16")
+
+    def __call__(self, x: torch.Tensor, train: bool = False) -> torch.Tensor:
+        """x (B, n, D) -> (B, 1, D) fp32 (attention.py:131-150). train=True would only turn the
+        MLP dropouts on; the head never passes it, and the build keeps them off."""
+        if train:
+            raise NotImplementedError("MultiHeadAttentionPooling(train=True): the head calls the "
+                                      "module without train (diffusion.py:99)")
+        if x.dim() != 3:
+            raise ValueError(f"x must be (batch, tokens, features), got {tuple(x.shape)}")
+        self._ensure(x.device, int(x.shape[-1]))
+        rows = torch.arange(x.shape[1], dtype=torch.int32, device=x.device)
+        out, _ = self.forward(x.float(), rows)
+        return out.float().unsqueeze(1)
+
+    def projected_query(self) -> torch.Tensor:
+        """(D,) fp32: (learnt_q_input . Wq + bq) / sqrt(Dh): the M = 1 product of the bf16
+        shadows with an fp32 output, then the scale."""
+        qp = self.query.fwd(self.probe.bf16.view(1, self.D), out_mode=K.OUT_F32)
+        return qp.view(self.D) * self.scale
+
+    # ------------------------------------------------------------------------------ forward
+    def forward(self, x: torch.Tensor, rows: torch.Tensor, out: torch.Tensor | None = None):
+        """x (B, L, D) fp32 (strided), rows (n,) int32: the pooled rows of every sample. Writes
+        the pooled embedding (B, D) bf16 into ``out`` (any row stride, e.g. the head's
+        readout_slot(cat)) and returns (out, saved)."""
+        B, D = x.shape[0], self.D
+        n = rows.numel()
+        if x.shape[2] != D:
+            raise ValueError(f"x has width {x.shape[2]}, the module {D}")
+        if not 1 <= n <= 64:
+            raise ValueError(f"attention pooling takes 1..64 tokens, got {n}")
+        r = K.rows_gather_bf16(x, rows).view(B * n, D)
+        kv = self.kv.fwd(r)
+        q = self.projected_query()
+        ctx, p = K.attn_pool_fwd(q, kv[:, :D], kv[:, D:], B, n, self.H)
+        a = self.out.fwd(ctx)                                     # (B, D) bf16: residual + LN input
+        if self.norm_axis == -1:
+            y, mu, rs = K.layernorm_fwd(a, self.ln.scale.data, self.ln.bias.data, self.eps)
+        else:
+            y, mu, rs = self.ln.fwd(a.view(B, 1, D))
+            y = y.view(B, D)
+        h = self.mlp.dense.fwd(y, act=K.ACT_RELU)
+        if out is None:
+            out = torch.empty((B, D), dtype=torch.bfloat16, device=x.device)
+        self.mlp.dense_out.fwd(h, residual=a, out=out)
+        return out, dict(B=B, n=n, r=r, kv=kv, q=q, ctx=ctx, p=p, a=a, y=y, mu=mu, rs=rs, h=h)
+
+    # ----------------------------------------------------------------------------- backward
+    def backward(self, de: torch.Tensor, sv: dict, row_flag: torch.Tensor) -> torch.Tensor:
+        """de (B, D) bf16 (any row stride): the gradient of the pooled embedding. row_flag (L,)
+        int32: the slot index of every pooled row of the sequence, -1 elsewhere. Accumulates every
+        parameter gradient and returns the whole dx (B, L, D) fp32 (zero outside the pooled rows)."""
+        B, n, D = sv["B"], sv["n"], self.D
+        h, a = sv["h"], sv["a"]
+        dz1 = self.mlp.dense_out.bwd(de, h, gate=h, gate_scale=1.0)   # relu backward in the epilogue
+        dy = self.mlp.dense.bwd(dz1, sv["y"])
+        if self.norm_axis == -1:
+            da, dyxh = K.layernorm_bwd(dy, a, sv["mu"], sv["rs"], self.ln.scale.data, addend=de)
+            K.colsum(dyxh, self.ln.scale.grad)
+            K.colsum(dy, self.ln.bias.grad)
+        else:
+            da = self.ln.bwd(dy.view(B, 1, D), a.view(B, 1, D), sv["mu"], sv["rs"],
+                             addend=de.unsqueeze(1)).view(B, D)
+        dctx = self.out.bwd(da, sv["ctx"])
+        kv = sv["kv"]
+        dkv = torch.empty_like(kv)
+        _, _, dqb = K.attn_pool_bwd(dctx, sv["p"], sv["q"], kv[:, :D], kv[:, D:],
+                                    dk=dkv[:, :D], dv=dkv[:, D:])
+        self._query_backward(dqb)
+        dr = self.kv.bwd(dkv, sv["r"])
+        return K.rows_scatter_bwd(dr.view(B, n, D), row_flag)
+
+    def _query_backward(self, dqb: torch.Tensor):
+        """d(query bias) += scale sum_b dqb through mmt_colsum into the flat gradient (in
+        deterministic mode through its fixed-point shadow, flushed here for this one bias so the
+        sum can be read back). From it d(learnt_q_input) = g . Wq, the M = 1 dX product, and the
+        rank-1 d(query kernel) = g^T probe, elementwise (a reduction of length 1)."""
+        D = self.D
+        bq, wq = self.query.b, self.query.w
+        dqb.mul_(self.scale)
+        before = bq.grad.clone()
+        K.colsum(dqb, bq.grad)
+        if self._store is not None:
+            self._store.det_flush(bq.offset, bq.offset + D)
+        g = (bq.grad - before).view(1, D)
+        wq.grad.addcmul_(g.view(D, 1), self.probe.bf16.view(1, D).float())
+        dprobe = K.gemm(g.to(torch.bfloat16), wq.bf16_t, trans_b=True, out_mode=K.OUT_F32)
+        self.probe.grad.view(1, D).add_(dprobe)
 
 
 class Encoder1DBlock(Bindable):

@@ -206,7 +206,56 @@ def _rules(model) -> Dict[str, Rule]:
         for d in ("Dense_0", "Dense_1"):
             rules[f"{ours}/{blk}/{d}/kernel"] = ([f"{hd}/{blk}/{d}/kernel"], _dense_T, _dense_T)
             rules[f"{ours}/{blk}/{d}/bias"] = ([f"{hd}/{blk}/{d}/bias"], _ident, _ident)
+    pool = getattr(model, "pooling", None)
+    if pool is not None:
+        # MultiHeadAttentionPooling (attention.py:122-150), the head's setup attribute `pooling`
+        # (diffusion.py:78); loading also accepts the class auto-name. The fused kv kernel is
+        # split into key / value apart from these one-to-one rules (_pool_kv).
+        D, H, Dh = pool.D, pool.H, pool.Dh
+        ours = POOL
+        cands = lambda leaf: [f"{c}/{leaf}" for c in POOL_FLAX]   # noqa: E731
+        mha = "MultiHeadDotProductAttention_0"
+        rules[f"{ours}/learnt_q_input"] = (cands("learnt_q_input"), _ident, _ident)
+        rules[f"{ours}/{mha}/query/kernel"] = (
+            cands(f"{mha}/query/kernel"), lambda a: np.ascontiguousarray(a.T.reshape(D, H, Dh)),
+            lambda a: np.ascontiguousarray(a.reshape(D, H * Dh).T))
+        rules[f"{ours}/{mha}/query/bias"] = (cands(f"{mha}/query/bias"),
+                                             lambda a: np.ascontiguousarray(a.reshape(H, Dh)),
+                                             lambda a: np.ascontiguousarray(a.reshape(-1)))
+        rules[f"{ours}/{mha}/out/kernel"] = (
+            cands(f"{mha}/out/kernel"), lambda a: np.ascontiguousarray(a.T.reshape(H, Dh, D)),
+            lambda a: np.ascontiguousarray(a.reshape(H * Dh, D).T))
+        rules[f"{ours}/{mha}/out/bias"] = (cands(f"{mha}/out/bias"), _ident, _ident)
+        for leaf in ("scale", "bias"):
+            rules[f"{ours}/LayerNorm_0/{leaf}"] = (cands(f"LayerNorm_0/{leaf}"), _ident, _ident)
+        for d in ("Dense_0", "Dense_1"):
+            rules[f"{ours}/MLPBlock_0/{d}/kernel"] = (cands(f"MLPBlock_0/{d}/kernel"), _dense_T,
+                                                      _dense_T)
+            rules[f"{ours}/MLPBlock_0/{d}/bias"] = (cands(f"MLPBlock_0/{d}/bias"), _ident, _ident)
     return rules
+
+
+POOL = "diffusion_action_head/MultiHeadAttentionPooling_0"
+POOL_FLAX = ("diffusion_action_head/pooling", POOL)
+
+
+def _pool_kv(model):
+    """The pooling module's fused kv Dense as its Flax leaves: [(leaf under the module,
+    rows of the fused parameter, export ours -> flax, import flax -> ours)] for key / value
+    kernel (D, H, Dh) and bias (H, Dh), the blocks' fused-QKV convention."""
+    pool = model.pooling
+    D, H, Dh = pool.D, pool.H, pool.Dh
+    mha = "MultiHeadDotProductAttention_0"
+    out = []
+    for j, n in enumerate(("key", "value")):
+        sl = slice(j * D, (j + 1) * D)
+        out.append((f"{mha}/{n}/kernel", f"{POOL}/{mha}/kv/kernel", sl,
+                    lambda a: np.ascontiguousarray(a.T.reshape(D, H, Dh)),
+                    lambda a: np.ascontiguousarray(a.reshape(D, H * Dh).T)))
+        out.append((f"{mha}/{n}/bias", f"{POOL}/{mha}/kv/bias", sl,
+                    lambda a: np.ascontiguousarray(a.reshape(H, Dh)),
+                    lambda a: np.ascontiguousarray(a.reshape(-1))))
+    return out
 
 
 SCAN = "attention_blocks/ScanEncoder1DBlock_0"
@@ -267,6 +316,10 @@ def to_flax_params(model) -> dict:
     for leaf, exp, _imp in _block_leaves(model):
         arr = np.stack([exp(b).detach().float().cpu().numpy() for b in blocks])
         _set(tree, f"{SCAN}/{leaf}", np.ascontiguousarray(arr.astype(np.float32)))
+    if getattr(model, "pooling", None) is not None:
+        for leaf, name, sl, exp, _imp in _pool_kv(model):
+            _set(tree, f"{POOL_FLAX[0]}/{leaf}",
+                 exp(by_name[name].data[sl].detach().float().cpu().numpy()))
     return tree
 
 
@@ -301,6 +354,19 @@ def load_flax_params(model, tree: dict, strict: bool = True) -> List[str]:
                 cpu = _CpuBlock(b)
                 fn(cpu, arr[i])
                 cpu.flush()
+        if getattr(model, "pooling", None) is not None:
+            for leaf, name, sl, _exp, imp in _pool_kv(model):
+                val = next((v for v in (_get(tree, f"{c}/{leaf}") for c in POOL_FLAX)
+                            if v is not None), None)
+                if val is None:
+                    missing.append(f"{name}[{leaf}]")
+                    continue
+                p = by_name[name]
+                val = imp(np.asarray(val, dtype=np.float32))
+                if tuple(val.shape) != tuple(p.data[sl].shape):
+                    raise ValueError(f"{name}: tree leaf {leaf} gives {val.shape}, expected "
+                                     f"{tuple(p.data[sl].shape)}")
+                p.data[sl].copy_(torch.from_numpy(val).to(p.data.device))
     if strict and missing:
         raise KeyError(f"parameters missing from the tree: {missing[:8]}")
     model.store.sync_shadow()

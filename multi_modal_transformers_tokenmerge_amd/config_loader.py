@@ -16,7 +16,9 @@ which are not available on the GPU box.
   reads (``attention_blocks.stacked_encoder_1d_block.{num_blocks, encoder_1d_block}``,
   ``octo.py:67,80``). New keys: ``token_compression_sequence`` (ToMe),
   ``token_compression_method`` ("tome" | "prune"), ``proportional_attention`` (ToMe's log-size
-  key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``fp8_matmul``, ``t5_num_layers`` and ``text_tokens``.
+  key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``readout_pooling`` ("mean" |
+  "attention": MultiHeadAttentionPooling of the readouts in the diffusion head, with
+  ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node), ``fp8_matmul``, ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
 ``KeyError`` / ``ValueError`` (Hydra raises on both).
@@ -276,6 +278,19 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     kw["compression"] = str(cfg.get("token_compression_method", "tome"))
     kw["proportional_attention"] = bool(cfg.get("proportional_attention", False))
     kw["track_merge_source"] = bool(cfg.get("track_merge_source", False))
+    # readout pooling of the diffusion head: the root keys, else the head's attention_pooling node
+    # (diffusion.yaml:6-51 of the reference: dot_product_attention.num_heads,
+    # mlp_block.dense.features, layer_norm.reduction_axes)
+    ap = diff.get("attention_pooling") or {}
+    kw["readout_pooling"] = str(cfg.get("readout_pooling", "mean"))
+    ph = cfg.get("pooling_heads", _first(ap, "dot_product_attention.num_heads", default=None))
+    pm = cfg.get("pooling_mlp_dim", _first(ap, "mlp_block.dense.features", default=None))
+    kw["pooling_heads"] = None if ph is None else int(ph)
+    kw["pooling_mlp_dim"] = None if pm is None else int(pm)
+    axes = _first(ap, "layer_norm.reduction_axes", default=None)
+    if axes is not None:
+        kw["pooling_norm_axes"] = tuple(int(v) for v in (axes if isinstance(axes, (list, tuple))
+                                                         else [axes]))
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

@@ -64,8 +64,28 @@ class OctoConfig:
     # with the step), read back with Octo.merge_source. Needs compression == "tome"; a no-op
     # without token_compression_sequence
     track_merge_source: bool = False
+    # how the diffusion head turns the readout tokens into its conditioning vector (YAML key
+    # readout_pooling): "mean" (the reference's live code path, diffusion.py:102) or "attention"
+    # (MultiHeadAttentionPooling, attention.py:122-150, the call the reference left commented out,
+    # diffusion.py:99): a learnt query attends to the readouts. pooling_heads: its head count
+    # (None: num_heads); pooling_mlp_dim: its MLPBlock's hidden width (None: token_embedding_dim,
+    # as in the reference's diffusion.yaml); pooling_norm_axes: its LayerNorm's reduction_axes,
+    # [-1] (the features) or [1] (the reference YAML's value: on the length-1 pooled sequence the
+    # norm then outputs its bias). The continuous and categorical heads keep their means.
+    readout_pooling: str = "mean"
+    pooling_heads: Optional[int] = None
+    pooling_mlp_dim: Optional[int] = None
+    pooling_norm_axes: tuple = (-1,)
 
     def __post_init__(self):
+        if self.readout_pooling not in ("mean", "attention"):
+            raise ValueError(f"readout_pooling must be 'mean' or 'attention', got "
+                             f"{self.readout_pooling!r}")
+        ph = self.pooling_heads if self.pooling_heads is not None else self.num_heads
+        if (self.readout_pooling == "attention" or self.pooling_heads is not None) and \
+                (ph < 1 or self.token_embedding_dim % ph):
+            raise ValueError(f"pooling_heads {ph} must divide token_embedding_dim "
+                             f"{self.token_embedding_dim}")
         if self.proportional_attention and self.compression != "tome":
             raise ValueError(f"proportional_attention needs compression='tome' (token sizes), got "
                              f"{self.compression!r}")
@@ -113,6 +133,10 @@ PRESETS = {
         name="octo-base-hires-tome32", token_embedding_dim=768, num_heads=12, mlp_dim=3072,
         image_size=(512, 512, 3), input_sequence="[TaskDescriptionPrefix{32}] [Image{1024};Readout{4}]",
         token_compression_sequence="[TaskDescriptionPrefix{0}] [Image{32};Readout{0}]", fp8=True),
+    # configs[2] with the readouts pooled by attention (6 heads, feature-axis LayerNorm)
+    "octo-small-tome16-map": OctoConfig(name="octo-small-tome16-map",
+                                        token_compression_sequence=TOME16,
+                                        readout_pooling="attention", pooling_heads=6),
     # top-k pruning on the small geometry: 16 image tokens per block
     "octo-small-prune16": OctoConfig(name="octo-small-prune16", token_compression_sequence=TOME16,
                                      compression="prune"),

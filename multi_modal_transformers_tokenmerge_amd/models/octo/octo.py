@@ -33,7 +33,8 @@ from ...tracing import phase
 from ...action_heads.categorical import CategoricalActionHead
 from ...action_heads.continuous import ContinuousActionHead
 from ...action_heads.diffusion import DiffusionActionHead
-from ...attention_blocks.attention import LayerCtx, StackedEncoder1DBlock
+from ...attention_blocks.attention import (LayerCtx, MultiHeadAttentionPooling,
+                                           StackedEncoder1DBlock)
 from ...layers import Dense, wgrad_overlap
 from ...params import ParamStore, he_normal, normal
 from ...schedules import Constant, Schedule, WarmupCosine, WarmupRsqrt
@@ -106,6 +107,15 @@ class Octo:
             self.categorical_head = CategoricalActionHead(store, "categorical_action_head", D,
                                                           cfg.action_space_dim, cfg.num_bins,
                                                           cfg.max_action)
+        # readout pooling by attention (OctoConfig.readout_pooling): declared after every head, so
+        # the offsets of all the parameters above are those of the "mean" configuration
+        self.pooling = None
+        if cfg.readout_pooling == "attention":
+            self.pooling = MultiHeadAttentionPooling.create(
+                store, "diffusion_action_head/MultiHeadAttentionPooling_0", D,
+                cfg.pooling_heads or cfg.num_heads, cfg.pooling_mlp_dim or D, cfg.layer_norm_eps,
+                cfg.pooling_norm_axes)
+            self.head.attach_pooling(self.pooling)
         store.materialize(self.device, seed)
         # MMT_DETERMINISTIC=1: bitwise-reproducible gradients (ParamStore.set_deterministic)
         if os.environ.get("MMT_DETERMINISTIC", "0") == "1" and torch.device(self.device).type == "cuda":
@@ -276,9 +286,14 @@ class Octo:
                                         inject.get("positions"), inject.get("tome"), t5_out)
         B = xL.shape[0]
         cat = self.head.new_cat(B, xL.device)
-        _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
-                _C.ptr(self.readout_rows), self.readout_rows.numel(),
-                _C.ptr(self.head.readout_slot(cat)), cat.stride(0), _C.stream_ptr())
+        if self.pooling is not None:
+            with phase("fwd/pool"):
+                _, st["pool_sv"] = self.pooling.forward(xL, self.readout_rows,
+                                                        out=self.head.readout_slot(cat))
+        else:
+            _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
+                    _C.ptr(self.readout_rows), self.readout_rows.numel(),
+                    _C.ptr(self.head.readout_slot(cat)), cat.stride(0), _C.stream_ptr())
         with phase("fwd/head"):
             loss, hsv = self.head.loss_forward(cat, actions, rng, sample_offset, inject.get("t"),
                                                inject.get("eps"))
@@ -287,9 +302,10 @@ class Octo:
 
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
                                        sample_offset=0, train=True):
-        """Reference :130-137: readouts -> readout mean -> OctoDenoise (diffusion.py:88-107)."""
+        """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
+        pooling) -> OctoDenoise (diffusion.py:88-107)."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
-        return self.head.predict_denoise_term_mean(self._readout_mean(xL), time, noisy_actions)
+        return self.head.predict_denoise_term_mean(self._readout_pooled(xL), time, noisy_actions)
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
@@ -298,12 +314,22 @@ class Octo:
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
         the 32-step DDPM sampler (action_heads/diffusion.py:146-209). Returns (B, 8) fp32."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions)
-        B = xL.shape[0]
-        e = torch.empty((B, self.D), dtype=torch.bfloat16, device=xL.device)
-        _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
-                _C.ptr(self.readout_rows), self.readout_rows.numel(), _C.ptr(e), e.stride(0),
-                _C.stream_ptr())
+        if self.pooling is not None:
+            e = self._readout_pooled(xL)
+        else:
+            B = xL.shape[0]
+            e = torch.empty((B, self.D), dtype=torch.bfloat16, device=xL.device)
+            _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
+                    _C.ptr(self.readout_rows), self.readout_rows.numel(), _C.ptr(e), e.stride(0),
+                    _C.stream_ptr())
         return self.head.predict_action_mean(e, rng, sample_offset, z, return_noise)
+
+    def _readout_pooled(self, xL):
+        """The diffusion head's conditioning vector (B, D) bf16: the readout mean, or the
+        attention pooling of the readout rows (OctoConfig.readout_pooling)."""
+        if self.pooling is None:
+            return self._readout_mean(xL)
+        return self.pooling.forward(xL, self.readout_rows)[0]
 
     # ------------------------------------------------------------------ other action heads
     def _readout_mean(self, xL):
@@ -458,6 +484,10 @@ class Octo:
         else:
             head = self.continuous_head if kind == "continuous" else self.head
             de = head.loss_backward(st["head_sv"])
+            if kind == "diffusion" and self.pooling is not None:
+                # readout_flag holds each readout row's slot index: the scatter writes all of dxL
+                with phase("bwd/pool"):
+                    return self.pooling.backward(de, st["pool_sv"], self.readout_flag)
             dxL = torch.empty(st["xL_shape"], dtype=torch.float32, device=de.device)
             _C.call("mmt_rows_mean_bwd", _C.ptr(de), de.stride(0), B, self.L_final, D,
                     _C.ptr(self.readout_flag), self.readout_rows.numel(), _C.ptr(dxL),
