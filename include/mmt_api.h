@@ -238,7 +238,9 @@ int mmt_topk_scatter_bwd(const void* dout, int dtype, int B, int K, int D, int64
  * the weight-gradient form; no other epilogue; with split_k > 1 the K range is split over
  * workgroups writing fp32 partial slabs into `workspace` (>= split_k*M*N floats, 16-B aligned)
  * which a second kernel sums into C — deterministic, no atomics).
- * Batched: blockIdx.z = batch index, with element strides sA, sB, sC.
+ * Batched: entry z of `batch` reads A + z*sA, B + z*sB and writes C + z*sC (element strides; sB = 0
+ * shares one weight). gate, residual and dropout are indexed by the row within an entry, so they
+ * are shared by all entries (bias is per column, so shared as well). Split-K needs batch == 1.
  * N, ldc and sC must be multiples of 8 (8-column vector epilogue); A, B, C 16-B aligned.
  * Epilogue order: v = alpha*acc + bias[n]; act; v *= (gate[m][n] > 0 ? gate_scale : 0);
  * dropout (flax.linen.Dropout with a counter-based stream: element idx = (drop_row_offset + m)*N
@@ -291,6 +293,38 @@ typedef struct {
  * waves; 4 = direct-to-LDS (global_load_lds) 128x128 kernel for NT; -1 = automatic (default).
  * Process-wide, not thread-safe. */
 void mmt_gemm_set_variant(int variant);
+/* The kernel that the last mmt_gemm / mmt_gemm_fp8 / mmt_gemm_xs call launched, so that a test
+ * can assert that it ran the kernel it is about: one value per kernel template that differs in
+ * addressing, MMT_GEMM_ROUTE_NONE after a call rejected before any launch. For the narrow NT
+ * kernel the tile width and the tile height of the call's last launch are encoded beside the
+ * value (MMT_GEMM_ROUTE_NTW_BN / _MT). MMT_GEMM_ROUTE_COMBINE is set as well when the split-K
+ * combine kernel ran after the main kernel. Process-wide, not thread-safe. */
+enum {
+  MMT_GEMM_ROUTE_NONE = 0,
+  MMT_GEMM_ROUTE_GENERIC_P0 = 1,       /* 128x128 register-staged, double-buffered (variant 0) */
+  MMT_GEMM_ROUTE_GENERIC_P1 = 2,       /* 128x128 single LDS stage, 64-deep K-steps (1) */
+  MMT_GEMM_ROUTE_GENERIC_P1_BK128 = 3, /* 128x128 single LDS stage, 128-deep K-steps (2) */
+  MMT_GEMM_ROUTE_BIG = 4,              /* 256x192 tiles (3) */
+  MMT_GEMM_ROUTE_GLDS_NT = 5,          /* direct-to-LDS 128x128 NT kernel (4) */
+  MMT_GEMM_ROUTE_NT256_256 = 6,        /* persistent 256 x BN NT kernel, BN 256 / 192 / 128 */
+  MMT_GEMM_ROUTE_NT256_192 = 7,
+  MMT_GEMM_ROUTE_NT256_128 = 8,
+  MMT_GEMM_ROUTE_NTW = 9,              /* narrow-output NT kernel; | bn / 64 << 8 | mt / 64 << 12 */
+  MMT_GEMM_ROUTE_NTWS = 10,            /* warp-specialised wide NT kernel */
+  MMT_GEMM_ROUTE_XS = 11,              /* activation-stationary K = 384 kernel */
+  MMT_GEMM_ROUTE_TN_DMA_256 = 12,      /* TN split-K slabs, two-stage, 32x32x16 MFMAs */
+  MMT_GEMM_ROUTE_TN_DMA_384 = 13,
+  MMT_GEMM_ROUTE_TN_DMA16_256 = 14,    /* TN split-K slabs, two-stage, 16x16x32 MFMAs */
+  MMT_GEMM_ROUTE_TN_DMA16_384 = 15,
+  MMT_GEMM_ROUTE_TN_R4_384 = 16,       /* TN split-K slabs, four-stage ring */
+  MMT_GEMM_ROUTE_FP8_NT = 17,          /* mmt_gemm_fp8's own NT kernel */
+  MMT_GEMM_ROUTE_XS_FP8 = 18,          /* activation-stationary kernel on e4m3 operands */
+  MMT_GEMM_ROUTE_KERNEL_MASK = 0xff,
+  MMT_GEMM_ROUTE_COMBINE = 0x10000
+};
+#define MMT_GEMM_ROUTE_NTW_BN(route) ((((route) >> 8) & 0xf) * 64)
+#define MMT_GEMM_ROUTE_NTW_MT(route) ((((route) >> 12) & 0xf) * 64)
+int mmt_gemm_last_route(void);
 /* Rows of the epilogue's colsum slab for this launch shape (ceil(M / 256)), 0 when the kernel the
  * launch would use cannot write it (then take the column sums with mmt_colsum). */
 int mmt_gemm_colsum_rows(int M, int N, int K, int transA, int transB, int c_mode, int split_k);

@@ -43,6 +43,7 @@ SIGNATURES: dict[str, list] = {
     "mmt_topk_gather": [P, I, I, I, I, L, L, P, L, I, P, P, P, P, L, L, P, P],
     "mmt_topk_scatter_bwd": [P, I, I, I, I, L, L, P, I, P, L, L, P],
     "mmt_gemm_set_variant": [I],
+    "mmt_gemm_last_route": [],
     "mmt_set_deterministic": [P, P, L],
     "mmt_det_flush": [P, P, L, P],
     "mmt_gemm_colsum_rows": [I, I, I, I, I, I, I],
@@ -113,6 +114,7 @@ SIGNATURES: dict[str, list] = {
 _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)
             "mmt_gemm_colsum_rows": I,    # returns a row count
+            "mmt_gemm_last_route": I,     # returns a ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -182,6 +184,23 @@ WS_TOME_MATCH, WS_GRAD_NORM = 1, 2  # mmt_workspace_size op codes (include/mmt_a
 GRAD_NORM_GRID = 2048
 OPT_WORDS = 8
 OPT_GRAD_NORM, OPT_CLIP, OPT_GMUL, OPT_LR, OPT_NONFINITE, OPT_SKIPPED, OPT_SKIP = range(7)
+
+
+# MMT_GEMM_ROUTE_* (include/mmt_api.h): what mmt_gemm_last_route() reports
+(ROUTE_NONE, ROUTE_GENERIC_P0, ROUTE_GENERIC_P1, ROUTE_GENERIC_P1_BK128, ROUTE_BIG, ROUTE_GLDS_NT,
+ ROUTE_NT256_256, ROUTE_NT256_192, ROUTE_NT256_128, ROUTE_NTW, ROUTE_NTWS, ROUTE_XS,
+ ROUTE_TN_DMA_256, ROUTE_TN_DMA_384, ROUTE_TN_DMA16_256, ROUTE_TN_DMA16_384, ROUTE_TN_R4_384,
+ ROUTE_FP8_NT, ROUTE_XS_FP8) = range(19)
+ROUTE_KERNEL_MASK, ROUTE_COMBINE = 0xff, 0x10000
+
+
+def route_ntw(bn: int, mt: int) -> int:
+    """The route of gemm_ntw_kernel with bn-wide tiles whose last launch used mt-row tiles."""
+    return ROUTE_NTW | (bn // 64) << 8 | (mt // 64) << 12
+
+
+def last_route() -> int:
+    return call("mmt_gemm_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

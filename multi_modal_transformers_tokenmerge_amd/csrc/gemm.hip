@@ -90,6 +90,9 @@ struct Geom {
 // tuning knob: 0 = PIPE 0 / BK 64, 1 = PIPE 1 / BK 64, 2 = PIPE 1 / BK 128, 3 = 256 x 192 tiles,
 // 4 = direct-to-LDS NT kernel; other = automatic (see mmt_gemm)
 int g_variant = -1;
+// the kernel of the last mmt_gemm / mmt_gemm_fp8 / mmt_gemm_xs launch (MMT_GEMM_ROUTE_*, include/
+// mmt_api.h; mmt_gemm_last_route): mmt::g_gemm_route (gemm_xs.h), set next to every launch below
+using mmt::g_gemm_route;
 
 struct Epi {
   const float* bias;
@@ -2642,11 +2645,17 @@ extern "C" int mmt_gemm_colsum_rows(int M, int N, int K, int transA, int transB,
 
 extern "C" void mmt_gemm_set_variant(int v) { g_variant = v; }
 
+namespace mmt {
+int g_gemm_route = MMT_GEMM_ROUTE_NONE;
+}
+extern "C" int mmt_gemm_last_route(void) { return mmt::g_gemm_route; }
+
 extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t lda,
                         const void* B, int transB, int64_t ldb, void* C, int c_mode, int64_t ldc,
                         int batch, int64_t sA, int64_t sB, int64_t sC, int split_k,
                         const mmt_epilogue_t* e, float* workspace, int64_t ws_elems,
                         mmt_stream_t stream) {
+  g_gemm_route = MMT_GEMM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(A && B && C, "mmt_gemm: null pointer");
   MMT_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0 && split_k > 0, "mmt_gemm: bad shape");
   MMT_CHECK_ARG(c_mode >= MMT_OUT_BF16 && c_mode <= MMT_OUT_F32_ACCUM, "mmt_gemm: c_mode");
@@ -2721,6 +2730,8 @@ extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t 
       const bf16_t* a = (const bf16_t*)A + (int64_t)r0 * lda;
       bf16_t* c = (bf16_t*)C + (int64_t)r0 * ldc;
       const bf16_t* r = epi.residual ? (const bf16_t*)epi.residual + (int64_t)r0 * epi.ld_res : nullptr;
+      // tile width and height beside the value (MMT_GEMM_ROUTE_NTW_BN / _MT), of the last launch
+      g_gemm_route = MMT_GEMM_ROUTE_NTW | (plan.bn / 64) << 8 | (mt / 64) << 12;
 #define GW(MTV, BNV)                                                                                  \
   do {                                                                                                 \
     if (ep == 0)                                                                                       \
@@ -2786,6 +2797,7 @@ extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t 
     const int tn = N / 128, n_tiles = ((M + 255) / 256) * tn;
     int grid = std::min(n_tiles, cu_count());
     if (grid > 8) grid &= ~7;
+    g_gemm_route = MMT_GEMM_ROUTE_NTWS;
 #define GWS(CSV, GBV)                                                                                   \
   hipLaunchKernelGGL((gemm_ntws_kernel<CSV, GBV>), dim3(grid), dim3(WS_NT), 0, s, M, N, K,              \
                      (const bf16_t*)A, lda, (const bf16_t*)B, ldb, (bf16_t*)C, ldc, tn, n_tiles, epi)
@@ -2811,6 +2823,8 @@ extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t 
     {
       const int tn = N / bn, n_tiles = ((M + 255) / 256) * tn;
       const int grid = std::min(n_tiles, n_cu);
+      g_gemm_route = bn == 256 ? MMT_GEMM_ROUTE_NT256_256
+                     : bn == 192 ? MMT_GEMM_ROUTE_NT256_192 : MMT_GEMM_ROUTE_NT256_128;
 #define GN(BNV, OUT, ST, NSV)                                                                     \
   hipLaunchKernelGGL((gemm_nt256_kernel<BNV, OUT, ST, NSV>), dim3(grid), dim3(NT3), 0, s, M, N, K, \
                      (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, tn, n_tiles, g_nt_xcd_order, epi)
@@ -2901,25 +2915,36 @@ extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t 
     // the ring with its DMA between the MFMA groups, the ring in two barrier-separated phases
     static const int g_tn_kernel = getenv("MMT_TN_KERNEL") ? atoi(getenv("MMT_TN_KERNEL")) : 13;
     const int tnk = (g_variant == 10 || g_variant == 13 || g_variant == 18) ? g_variant : g_tn_kernel;
-    if ((tnk == 18 || (tnk == 13 && g_variant < 10 && k_chunk <= 2048)) && tall)
+    if ((tnk == 18 || (tnk == 13 && g_variant < 10 && k_chunk <= 2048)) && tall) {
+      g_gemm_route = MMT_GEMM_ROUTE_TN_R4_384;
       hipLaunchKernelGGL(gemm_tn_r4_kernel<384>, dim3(work), dim3(TN_NT), 0, s, M, N, K,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, workspace, split_k, k_chunk, tn);
-    else if (tnk == 13 && tall)
+    } else if (tnk == 13 && tall) {
+      g_gemm_route = MMT_GEMM_ROUTE_TN_DMA16_384;
       hipLaunchKernelGGL(gemm_tn_dma16_kernel<384>, dim3(work), dim3(TN_NT), 0, s, M, N, K,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, workspace, split_k, k_chunk, tn);
-    else if (tnk == 13 || tnk == 18)
+    } else if (tnk == 13 || tnk == 18) {
+      g_gemm_route = MMT_GEMM_ROUTE_TN_DMA16_256;
       hipLaunchKernelGGL(gemm_tn_dma16_kernel<256>, dim3(work), dim3(TN_NT), 0, s, M, N, K,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, workspace, split_k, k_chunk, tn);
-    else if (tall)
+    } else if (tall) {
+      g_gemm_route = MMT_GEMM_ROUTE_TN_DMA_384;
       hipLaunchKernelGGL(gemm_tn_dma_kernel<384>, dim3(work), dim3(TN_NT), 0, s, M, N, K,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, workspace, split_k, k_chunk, tn);
-    else
+    } else {
+      g_gemm_route = MMT_GEMM_ROUTE_TN_DMA_256;
       hipLaunchKernelGGL(gemm_tn_dma_kernel<256>, dim3(work), dim3(TN_NT), 0, s, M, N, K,
                          (const bf16_t*)A, lda, (const bf16_t*)B, ldb, workspace, split_k, k_chunk, tn);
+    }
     MMT_CHECK_LAUNCH("mmt_gemm(tn dma)");
   } else {
 #define GL(TA, TB, OUT)                          \
   do {                                           \
+    g_gemm_route = pipe == 4   ? MMT_GEMM_ROUTE_GLDS_NT          \
+                   : pipe == 0 ? MMT_GEMM_ROUTE_GENERIC_P0       \
+                   : pipe == 1 ? MMT_GEMM_ROUTE_GENERIC_P1       \
+                   : pipe == 2 ? MMT_GEMM_ROUTE_GENERIC_P1_BK128 \
+                               : MMT_GEMM_ROUTE_BIG;             \
     if (pipe == 4) GLG(OUT);                     \
     else if (pipe == 0) GL1(TA, TB, OUT, 0, 64); \
     else if (pipe == 1) GL1(TA, TB, OUT, 1, 64); \
@@ -2946,6 +2971,7 @@ extern "C" int mmt_gemm(int M, int N, int K, const void* A, int transA, int64_t 
   if (out_kind == 2) {
     const int64_t n4 = (int64_t)M * N / 4;
     const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 8192);
+    g_gemm_route |= MMT_GEMM_ROUTE_COMBINE;
     if (final_kind == 0)
       hipLaunchKernelGGL(splitk_epilogue_kernel<0>, dim3(blocks), dim3(256), 0, s, workspace,
                          split_k, M, N, C, ldc, epi);
@@ -2971,6 +2997,7 @@ extern "C" int mmt_quant_rows_fp8(const void* x, int64_t ld, int rows, int K, vo
 extern "C" int mmt_gemm_fp8(int M, int N, int K, const void* A, int64_t lda, const float* sa,
                             const void* B, int64_t ldb, const float* sb, void* C, int c_mode,
                             int64_t ldc, const mmt_epilogue_t* e, mmt_stream_t stream) {
+  g_gemm_route = MMT_GEMM_ROUTE_NONE;
   MMT_CHECK_ARG(A && B && C && sa && sb && M > 0 && N > 0 && K > 0, "mmt_gemm_fp8: args");
   MMT_CHECK_ARG(K % 64 == 0 && N % 8 == 0 && lda % 16 == 0 && ldb % 16 == 0 && ldc % 8 == 0 &&
                     (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0 && (uintptr_t)C % 16 == 0 &&
@@ -3025,6 +3052,7 @@ extern "C" int mmt_gemm_fp8(int M, int N, int K, const void* A, int64_t lda, con
       return xs_launch(M, N, K, true, A, lda, B, ldb, C, ldc, 0, xe, s);
   }
   const int tiles_n = (N + F8_BN - 1) / F8_BN, n_work = ((M + F8_BM - 1) / F8_BM) * tiles_n;
+  g_gemm_route = MMT_GEMM_ROUTE_FP8_NT;
   if (c_mode == MMT_OUT_BF16)
     hipLaunchKernelGGL(gemm_fp8_nt_kernel<0>, dim3(n_work), dim3(256), 0, s, M, N, K,
                        (const uint8_t*)A, lda, sa, (const uint8_t*)B, ldb, sb, C, ldc, tiles_n,

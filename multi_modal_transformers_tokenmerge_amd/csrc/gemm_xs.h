@@ -4,6 +4,11 @@
 
 namespace mmt {
 
+// The kernel of the last mmt_gemm / mmt_gemm_fp8 / mmt_gemm_xs launch (MMT_GEMM_ROUTE_*, 0 after a
+// call rejected before its launch; defined in gemm.hip, read by mmt_gemm_last_route). Process-wide,
+// not thread-safe, like mmt_gemm_set_variant.
+extern int g_gemm_route;
+
 // The epilogue the activation-stationary kernel applies, in epilogue_w's order (gemm.hip):
 // v = acc (* sa[m] * sb[n] for fp8) * alpha + bias[n]; relu; dropout (counter RNG pair draws of
 // element (drop_row_offset + m) * N + n); + residual[m][n]; stored bf16 or fp32.

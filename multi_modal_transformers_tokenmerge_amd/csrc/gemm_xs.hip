@@ -373,6 +373,7 @@ int xs_launch(int M, int N, int K, bool f8, const void* X, int64_t lda, const vo
     n_cu = 256;
   const int grid = std::min(n_units, n_cu);
   const int esz = f8 ? 1 : 2;
+  g_gemm_route = f8 ? MMT_GEMM_ROUTE_XS_FP8 : MMT_GEMM_ROUTE_XS;
   if (f8)
     hipLaunchKernelGGL(gemm_xs_kernel<true>, dim3(grid), dim3(512), 0, stream, M, N, (const char*)X,
                        lda * esz, (const char*)W, ldb * esz, (bf16_t*)C, ldc, e, n_units);
@@ -391,6 +392,7 @@ int xs_launch(int M, int N, int K, bool f8, const void* X, int64_t lda, const vo
 extern "C" int mmt_gemm_xs(int M, int N, int K, const void* X, int64_t ldx, const void* W,
                            int64_t ldw, void* C, int64_t ldc, const float* bias,
                            mmt_stream_t stream) {
+  mmt::g_gemm_route = MMT_GEMM_ROUTE_NONE;
   MMT_CHECK_ARG(X && W && C && M > 0, "mmt_gemm_xs: bad args");
   XsEpi e;
   e.bias = bias;

@@ -91,8 +91,14 @@ def test_gemm_gate_and_beta_and_atomic_splitk(dev):
 @pytest.mark.parametrize("M,N,K", [(1536, 384, 16384), (1152, 384, 9997), (384, 1536, 12288),
                                    (640, 200, 30000), (384, 384, 20480)])
 def test_gemm_tn_splitk_weight_gradient(dev, M, N, K):
-    """The step's weight-gradient launches (TN, fp32 split-K slabs + combine, C += A^T B): the
-    direct-to-LDS TN kernel at full and partial M / N tiles and a partial last K-step."""
+    """The step's weight-gradient launches (TN, fp32 split-K slabs + combine, C += A^T B) with the
+    split layers.split_k_for picks: the four shapes with M % 384 == 0 run the direct-to-LDS ring
+    (gemm_tn_r4_kernel<384>: chunks of at most 2,048 rows) at full 384-row tiles, N a multiple of
+    192 and, at K = 9997, a partial last K-step. (640, 200, 30000) does not reach a TN kernel: its
+    3 x 2 x 21 = 126 work items are under mmt_gemm's floor of 128, so it runs the generic
+    single-stage gemm_kernel. The TN kernels' partial M / N tiles are covered by
+    tests/test_gemm_contract_gpu.py::test_tn_dma_kernels_partial_tiles. The route is asserted."""
+    from multi_modal_transformers_tokenmerge_amd import _C
     from multi_modal_transformers_tokenmerge_amd import _kernels as Kn
     from multi_modal_transformers_tokenmerge_amd.layers import split_k_for
     g = torch.Generator().manual_seed(M + N + K)
@@ -100,6 +106,8 @@ def test_gemm_tn_splitk_weight_gradient(dev, M, N, K):
     dw = torch.randn(M, N, generator=g).to(dev)
     ref = dw + dy.float().t() @ x.float()
     Kn.gemm(dy, x, trans_a=True, out=dw, out_mode=Kn.OUT_F32_ACCUM, split_k=split_k_for(M, N, K))
+    main = _C.ROUTE_TN_R4_384 if M % 384 == 0 else _C.ROUTE_GENERIC_P1
+    assert _C.last_route() == main | _C.ROUTE_COMBINE
     torch.testing.assert_close(dw, ref, rtol=1e-4, atol=1e-4 * ref.abs().max().item())
 
 
@@ -165,8 +173,11 @@ def test_t5_relu_product(dev):
 def test_narrow_nt_kernel(dev, M, N, K, ep, variant):
     """gemm_ntw_kernel (the products formerly on hipBLASLt: N <= 768 over K >= 1152, the T5 relu
     product; variant 8 forces it on any N % 192 == 0, K % 64 == 0 launch): ragged row counts,
-    the two-launch plan (full rounds of 256-row tiles + one round of smaller tiles at M = 138,496),
+    the launch plan of ntw_plan (asserted through the route: on 256 CUs M = 138,496 runs as one
+    launch of 192-row tiles and M = 9,000 x N = 3,072 as the two-launch plan, a full round of
+    256-row tiles + one round of 64-row tiles; the other shapes as one launch of 64-row tiles),
     residual and relu epilogues, against fp32 torch on the same bf16 operands."""
+    from tests.test_gemm_contract_gpu import _ntw_plan
     from multi_modal_transformers_tokenmerge_amd import _C
     from multi_modal_transformers_tokenmerge_amd import _kernels as Kn
     g = torch.Generator().manual_seed(M + N + K)
@@ -179,6 +190,8 @@ def test_narrow_nt_kernel(dev, M, N, K, ep, variant):
         torch.cuda.synchronize()
     finally:
         _C.call("mmt_gemm_set_variant", -1)
+    bn, rows_big, mt2 = _ntw_plan(M, N, torch.cuda.get_device_properties(dev).multi_processor_count)
+    assert _C.last_route() == _C.route_ntw(bn, mt2 if M > rows_big else 256)
     ref = a.float() @ b.float().t() + (r.float() if r is not None else 0.0)
     if ep == "relu":
         ref = ref.clamp_min(0)
@@ -195,6 +208,7 @@ def test_residual_stream_kernel(dev, M, N, K, alpha):
     reductions: the dropout keeps are the shared counter stream's (oracle/rng.py), the sum within
     fp32 accumulation order of a torch reference. (Round 4's warp-specialised kernel for these
     products measured slower and was deleted in round 6.)"""
+    from multi_modal_transformers_tokenmerge_amd import _C
     from multi_modal_transformers_tokenmerge_amd import _kernels as Kn
     g = torch.Generator().manual_seed(M + N + K)
     a, w = _mk((M, K), dev, g), _mk((N, K), dev, g)
@@ -204,6 +218,7 @@ def test_residual_stream_kernel(dev, M, N, K, alpha):
     kw = dict(bias=bias, rng=rng, drop_layer=2, drop_site=3, keep_prob=0.9, drop_row_offset=3 * M,
               residual=res, alpha=alpha, out_mode=Kn.OUT_F32)
     out = Kn.gemm(a, w, False, True, **kw)
+    assert _C.last_route() == _C.ROUTE_GLDS_NT
     torch.cuda.synchronize()
     keep = torch.from_numpy(R.dropout_mask_2d(31, 4, 2, 3, M, N, 3 * M, 0.9)).to(dev)
     ref = alpha * (a.float() @ w.float().t()) + bias
@@ -228,12 +243,16 @@ def test_activation_stationary_kernel(dev, M, N, bias):
     out = torch.full((M + 3, N), 7.0, dtype=torch.bfloat16, device=dev)  # rows past M: untouched
     _C.call("mmt_gemm_xs", M, N, K, a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N,
             None if b is None else b.data_ptr(), _C.stream_ptr())
+    assert _C.last_route() == _C.ROUTE_XS
     _C.call("mmt_gemm_set_variant", 4)
     try:
         old = Kn.gemm(a, w, False, True, bias=b)
+        assert _C.last_route() == _C.ROUTE_GLDS_NT
     finally:
         _C.call("mmt_gemm_set_variant", -1)
     disp = Kn.gemm(a, w, False, True, bias=b)  # mmt_gemm's own dispatch (XS where it applies)
+    # M = 700 is below the dispatch floor of 32,768 rows and has too few tiles for nt256
+    assert _C.last_route() == (_C.ROUTE_XS if M >= 32768 else _C.ROUTE_GLDS_NT)
     torch.cuda.synchronize()
     assert torch.equal(out[:M], old) and torch.equal(disp, old)
     assert bool((out[M:] == 7.0).all())
@@ -264,6 +283,7 @@ def test_activation_stationary_relu_bits(dev, M, row_off):
         try:
             h = Kn.gemm(y, w1, False, True, bias=bias, act=Kn.ACT_RELU, rng=rng, drop_layer=3,
                         drop_site=2, keep_prob=0.9, drop_row_offset=row_off, relu_bits=bits)
+            assert _C.last_route() == (_C.ROUTE_XS if v < 0 else _C.ROUTE_NT256_256)
         finally:
             _C.call("mmt_gemm_set_variant", -1)
         outs.append((h, bits))
@@ -279,12 +299,18 @@ def test_activation_stationary_relu_bits(dev, M, row_off):
                                          (384, 384, 20480, 16), (1536, 384, 141312, 32),
                                          (384, 384, 1040, 4), (768, 192, 48, 1)])
 def test_tn_kernels_bit_identical(dev, M, N, K, split):
-    """The TN weight-gradient kernels: the two-stage kernel on 32x32x16 MFMAs (variant 10), on
-    16x16x32 (13, the default) and the four-stage ring of 32-row K-steps (18, the default for
-    K chunks of at most 2,048 rows) — at the step's shapes (384-row tiles), partial M tiles
-    (256-row tiles), partial N tiles, ragged K, K chunks shorter than the ring and a split with a
-    single K-step; 13 and 18 share the per-k32 MFMA order (bit-identical), 10 groups k by 16
-    (fp32 rounding apart); all match an fp32 reference."""
+    """Variants 10 / 13 / 18 choose among the TN weight-gradient kernels: the two-stage kernel on
+    32x32x16 MFMAs (10), on 16x16x32 (13) and the four-stage ring of 32-row K-steps (18); 13 and
+    18 share the per-k32 MFMA order (bit-identical), 10 groups k by 16 (fp32 rounding apart); all
+    match an fp32 reference. Of these sets only (1536, 384, 141312, 32) reaches them (384-row
+    tiles, full N tiles, 4,416-row chunks: gemm_tn_dma_kernel<384> / gemm_tn_dma16_kernel<384> /
+    gemm_tn_r4_kernel<384>): mmt_gemm takes a TN kernel only from ceil(M/256) ceil(N/192) split
+    >= 128 work items, and the other split sets have 96 / 30 / 80 / 42 / 64 / 16, so all three
+    variants run the same generic gemm_kernel there (double-buffered over more than 24 K-steps
+    per chunk, else single-stage) and the comparison is of that kernel with itself;
+    (768, 192, 48, 1) has no slabs at all. The route each set takes is asserted. The TN kernels
+    on partial M / N tiles, ragged K and one-K-step chunks are covered by
+    tests/test_gemm_contract_gpu.py::test_tn_dma_kernels_partial_tiles."""
     from multi_modal_transformers_tokenmerge_amd import _kernels as Kn, _C
     g = torch.Generator().manual_seed(M * 7 + N + K)
     dy, x = _mk((K, M), dev, g), _mk((K, N), dev, g)
@@ -294,6 +320,13 @@ def test_tn_kernels_bit_identical(dev, M, N, K, split):
             _C.call("mmt_gemm_set_variant", v)
             dw = torch.zeros(M, N, device=dev)
             Kn.gemm(dy, x, trans_a=True, out=dw, out_mode=Kn.OUT_F32_ACCUM, split_k=split)
+            k_chunk = -(-(-(-K // split)) // 64) * 64
+            if split > 1 and -(-M // 256) * -(-N // 192) * -(-K // k_chunk) >= 128:
+                main = {10: _C.ROUTE_TN_DMA_384, 13: _C.ROUTE_TN_DMA16_384, 18: _C.ROUTE_TN_R4_384}[v]
+                assert M % 384 == 0
+            else:
+                main = _C.ROUTE_GENERIC_P0 if k_chunk // 64 > 24 else _C.ROUTE_GENERIC_P1
+            assert _C.last_route() == main | (_C.ROUTE_COMBINE if split > 1 else 0), (v, _C.last_route())
             torch.cuda.synchronize()
             outs[v] = dw
     finally:

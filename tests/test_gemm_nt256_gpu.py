@@ -13,6 +13,17 @@ pytestmark = pytest.mark.gpu
 VARIANTS = {256: 5, 192: 6, 128: 7}
 
 
+def _route():
+    from multi_modal_transformers_tokenmerge_amd import _C
+    return _C.last_route()
+
+
+def _nt256(bn):
+    """mmt_gemm_last_route() of gemm_nt256_kernel with bn-wide tiles."""
+    from multi_modal_transformers_tokenmerge_amd import _C
+    return {256: _C.ROUTE_NT256_256, 192: _C.ROUTE_NT256_192, 128: _C.ROUTE_NT256_128}[bn]
+
+
 def _mk(shape, dev, g):
     return torch.randn(shape, generator=g).to(torch.bfloat16).to(dev)
 
@@ -42,8 +53,10 @@ def test_nt256_plain(dev, variant, bn, M, K):
     a, w = _mk((M, K), dev, g), _mk((N, K), dev, g)
     ref = a.float() @ w.float().t()
     out = Kn.gemm(a, w, False, True, split_k=1)
+    assert _route() == _nt256(bn)
     _close_bf16(out, ref)
     out32 = Kn.gemm(a, w, False, True, out_mode=Kn.OUT_F32, split_k=1)
+    assert _route() == _nt256(bn)
     torch.testing.assert_close(out32, ref, rtol=1e-5, atol=1e-5 * ref.abs().max().item())
 
 
@@ -62,6 +75,7 @@ def test_nt256_epilogues(dev, variant, bn):
     res = _mk((M, N), dev, g)
     out = Kn.gemm(a, w, False, True, bias=bias, act=Kn.ACT_RELU, rng=rng, drop_layer=3,
                   drop_site=2, keep_prob=0.9, drop_row_offset=5 * M, residual=res, split_k=1)
+    assert _route() == _nt256(bn)
     ref = torch.where(keep, torch.relu(base + bias) / 0.9, torch.zeros_like(base)) + res.float()
     _close_bf16(out, ref)
     # dropout + fp32 residual, fp32 out (the residual-stream projections)
@@ -69,29 +83,35 @@ def test_nt256_epilogues(dev, variant, bn):
     out = Kn.gemm(a, w, False, True, bias=bias, rng=rng, drop_layer=3, drop_site=2,
                   keep_prob=0.9, drop_row_offset=5 * M, residual=res32, out_mode=Kn.OUT_F32,
                   split_k=1)
+    assert _route() == _nt256(bn)
     ref = torch.where(keep, (base + bias) / 0.9, torch.zeros_like(base)) + res32
     torch.testing.assert_close(out, ref, rtol=1e-5, atol=1e-4)
     # gate (relu-backward mask) and fp32 accumulate (beta = 1)
     gate = _mk((M, N), dev, g)
     out = Kn.gemm(a, w, False, True, gate=gate, gate_scale=1 / 0.9, split_k=1)
+    assert _route() == _nt256(bn)
     _close_bf16(out, base * (gate.float() > 0).float() / 0.9)
     c = torch.randn((M, N), generator=g).to(dev)
     c0 = c.clone()
     Kn.gemm(a, w, False, True, out=c, out_mode=Kn.OUT_F32, beta=1.0, split_k=1)
+    assert _route() == _nt256(bn)
     torch.testing.assert_close(c, c0 + base, rtol=1e-5, atol=1e-3)
 
 
 def test_nt256_auto_matches_reference_path(dev):
-    """Auto choice at a step shape (MLP up-projection, B = 64) vs the 128 x 128 glds kernel."""
+    """Auto choice at a step shape (MLP up-projection, B = 64: gemm_nt256_kernel with 256-wide
+    tiles) vs the 128 x 128 glds kernel."""
     from multi_modal_transformers_tokenmerge_amd import _kernels as Kn, _C
     g = torch.Generator().manual_seed(3)
     M, N, K = 64 * 276, 1536, 384
     a, w = _mk((M, K), dev, g), _mk((N, K), dev, g)
     bias = torch.randn(N, generator=g).to(dev)
     o_new = Kn.gemm(a, w, False, True, bias=bias, act=Kn.ACT_RELU, split_k=1)
+    assert _route() == _nt256(256)
     _C.call("mmt_gemm_set_variant", 4)
     try:
         o_old = Kn.gemm(a, w, False, True, bias=bias, act=Kn.ACT_RELU, split_k=1)
+        assert _route() == _C.ROUTE_GLDS_NT
     finally:
         _C.call("mmt_gemm_set_variant", -1)
     # identical accumulation order is not guaranteed across kernels: compare within 1 bf16 ulp
@@ -116,7 +136,9 @@ def test_nt256_colsum_slab(dev, variant, M):
     assert rows == (M + 255) // 256
     slab = torch.full((rows, N), float("nan"), dtype=torch.float32, device=dev)
     out = Kn.gemm(a, w, False, True, gate=gate, gate_scale=1.25, colsum=slab)
+    assert _route() == _nt256(256)
     plain = Kn.gemm(a, w, False, True, gate=gate, gate_scale=1.25)
+    assert _route() == _nt256(256)
     assert torch.equal(out, plain)
     pad = torch.zeros((rows * 256, N), dtype=torch.float64, device=dev)
     pad[:M] = out.double()
@@ -161,8 +183,10 @@ def test_relu_bits_and_gate_bits(dev, M):
     bits = torch.empty((-(-M // 256) * 256, N // 32), dtype=torch.int32, device=dev)
     h = Kn.gemm(y, w1, False, True, bias=bias, act=Kn.ACT_RELU, rng=rng, drop_layer=1, drop_site=2,
                 keep_prob=0.9, relu_bits=bits)
+    assert _route() == _nt256(256)
     h_ref = Kn.gemm(y, w1, False, True, bias=bias, act=Kn.ACT_RELU, rng=rng, drop_layer=1,
                     drop_site=2, keep_prob=0.9)
+    assert _route() == _nt256(256)
     assert torch.equal(h, h_ref)
     torch.testing.assert_close(_bits_to_mask(bits, M, N), h.float() > 0, rtol=0, atol=0)
     dz2, w2t = _mk((M, K), dev, g), _mk((N, K), dev, g)  # dX of a Dense with W2^T (N, K)
@@ -171,6 +195,7 @@ def test_relu_bits_and_gate_bits(dev, M):
     cs_b = torch.empty((rows, N), device=dev)
     d_a = Kn.gemm(dz2, w2t, False, True, gate=h, gate_scale=1 / 0.9, colsum=cs_a)
     d_b = Kn.gemm(dz2, w2t, False, True, gate_bits=bits, gate_scale=1 / 0.9, colsum=cs_b)
+    assert _route() == _nt256(256)
     assert torch.equal(d_a, d_b)
     assert torch.equal(cs_a, cs_b)
     d_c = Kn.gemm(dz2, w2t, False, True, gate_bits=bits, gate_scale=1 / 0.9)  # no column sums
@@ -197,8 +222,12 @@ def test_keep_bits_match_epilogue_draws(dev, M, row_off):
     b2 = torch.empty_like(b1)
     h1 = Kn.gemm(y, w1, False, True, bias=bias, act=Kn.ACT_RELU, rng=rng, drop_layer=4, drop_site=2,
                  keep_prob=0.9, drop_row_offset=row_off, relu_bits=b1)
+    # the epilogue-draw launch is the activation-stationary kernel's from 32,768 rows
+    from multi_modal_transformers_tokenmerge_amd import _C
+    assert _route() == (_C.ROUTE_XS if M >= 32768 else _nt256(256))
     h2 = Kn.gemm(y, w1, False, True, bias=bias, act=Kn.ACT_RELU, keep_bits=kb, keep_prob=0.9,
                  relu_bits=b2)
+    assert _route() == _nt256(256)
     assert torch.equal(h1, h2)
     assert torch.equal(b1, b2)
     with pytest.raises(ValueError):  # keep_bits replaces rng, only in a relu_bits launch
@@ -206,12 +235,16 @@ def test_keep_bits_match_epilogue_draws(dev, M, row_off):
 
 
 def test_bits_rejected_off_the_256_path(dev):
-    from multi_modal_transformers_tokenmerge_amd import _kernels as Kn
+    """The wrapper refuses the launch itself (no kernel runs); without the bit image the same
+    shape runs on the 128 x 128 glds kernel (too few tiles for nt256), which has no bit path."""
+    from multi_modal_transformers_tokenmerge_amd import _kernels as Kn, _C
     M, N, K = 300, 1536, 384
     assert not Kn.gemm_bits_supported(M, N, K)
     a, w = torch.zeros((M, K), dtype=torch.bfloat16, device=dev), torch.zeros((N, K), dtype=torch.bfloat16, device=dev)
     with pytest.raises(ValueError):
         Kn.gemm(a, w, False, True, relu_bits=torch.empty((512, N // 32), dtype=torch.int32, device=dev))
+    Kn.gemm(a, w, False, True)
+    assert _route() == _C.ROUTE_GLDS_NT
 
 
 @pytest.mark.parametrize("M,N,K", [(4133, 1536, 384), (70656, 1536, 384), (9000, 1152, 384),
@@ -244,6 +277,7 @@ def test_ntws_matches_nt256(dev, M, N, K):
                 if cs_ is not None:
                     extra["colsum"] = torch.full((rows, N), float("nan"), device=dev)
                 o = Kn.gemm(a, w, False, True, split_k=1, **kw, **extra)
+                assert _route() == (_C.ROUTE_NTWS if v < 0 else _nt256(256 if N % 256 == 0 else 192))
                 outs.append((o, extra))
             finally:
                 _C.call("mmt_gemm_set_variant", -1)
