@@ -381,7 +381,37 @@ int mmt_gemm_fp8(int M, int N, int K, const void* A, int64_t lda, const float* s
  * wsum (optional, fp32 (B, H, L)): per query, the sum over keys of the attention weights AFTER
  * dropout (kept / keep_prob) — the per-head factor of the pruning importance score
  * (compressed_attention.py:302-306: mean over keys, then over heads; mmt_prune_importance).
+ * Operand rules, the same for mmt_attn_fwd and mmt_attn_bwd (and their _keybias forms), checked
+ * before anything is launched (MMT_ERR_INVALID): the kernels move every bf16 operand (qkv, o,
+ * dout, dqkv) as 16-B vectors, so each base pointer is 16-B aligned and each row and batch
+ * stride (s_*, o_s_*, d_s_*, dq_s_*) is a multiple of 8 elements; a row stride is at least the
+ * row it carries (s_t, dq_s_t >= 3*H*Dh; o_s_t, d_s_t >= H*Dh); Dh is 64, 128 or 256;
+ * 0 < L <= 4096. Nothing outside rows [0, L) x the row width of a sample is read or written;
+ * lse and wsum are written at [0, B*H*L) and delta inside its documented size only.
  */
+/* The kernel that the last mmt_attn_fwd / mmt_attn_bwd (or _keybias) call launched, forward or
+ * backward, as mmt_gemm_last_route() reports the GEMM's: MMT_ATTN_ROUTE_NONE after a call
+ * rejected before any launch. Beside the kernel (MMT_ATTN_ROUTE_KERNEL_MASK) the value carries
+ * MMT_ATTN_ROUTE_PARAM — the tiled forward's query blocks per wave NQ (1 / 2), a resident kernel's
+ * NTILE (2 * ceil(L / 64): 2 .. 10), the tiled backward's waves per workgroup (2: 128 threads,
+ * 4: 256) — for the tiled kernels MMT_ATTN_ROUTE_DH, and MMT_ATTN_ROUTE_WORKLIST when the
+ * concurrent-phase backward took its blocks from the work list (NTILE 8 outside deterministic
+ * mode) instead of the static deal. Process-wide, not thread-safe. */
+enum {
+  MMT_ATTN_ROUTE_NONE = 0,
+  MMT_ATTN_ROUTE_FWD_TILED_1W = 1,    /* attn_fwd_kernel, one-wave workgroups (L <= 32) */
+  MMT_ATTN_ROUTE_FWD_TILED_4W = 2,    /* attn_fwd_kernel, four waves x NQ query blocks */
+  MMT_ATTN_ROUTE_FWD_RES_ONEPASS = 3, /* attn_fwd_res_kernel, online softmax (the default) */
+  MMT_ATTN_ROUTE_FWD_RES_TWOPASS = 4, /* attn_fwd_res_kernel, exact row max first */
+  MMT_ATTN_ROUTE_BWD_TILED = 5,       /* attn_bwd_dq_kernel + attn_bwd_dkdv_kernel */
+  MMT_ATTN_ROUTE_BWD_RES = 6,         /* attn_bwd_res_kernel: two-phase, 4 waves */
+  MMT_ATTN_ROUTE_BWD_RES8 = 7,        /* attn_bwd_res8_kernel: concurrent phases, 8 waves */
+  MMT_ATTN_ROUTE_KERNEL_MASK = 0xff,
+  MMT_ATTN_ROUTE_WORKLIST = 0x10000
+};
+#define MMT_ATTN_ROUTE_PARAM(route) (((route) >> 8) & 0xf)
+#define MMT_ATTN_ROUTE_DH(route) ((((route) >> 12) & 0xf) * 64)
+int mmt_attn_last_route(void);
 int mmt_attn_fwd(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H, int Dh,
                  float scale, int n_sets, const int32_t* set_start, const int32_t* set_len,
                  const uint32_t* set_vis, const uint32_t* drop_bits, float keep_prob,
@@ -404,7 +434,8 @@ int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H,
  * above. key_bias == NULL is mmt_attn_fwd / mmt_attn_bwd (which forward here with NULL).
  * key_bias: fp32, row b at key_bias + b*kb_s_b; kb_s_b a multiple of 4 and >= roundup(L, 64); the
  * base 16-B aligned. Entries [0, L) are used and must be finite; entries [L, roundup(L, 64)) must
- * be readable and are ignored (the kernels load aligned float4s, so L needs no multiple of 4).
+ * be readable and are ignored whatever they hold, NaN and Inf included (the kernels load aligned
+ * float4s, so L needs no multiple of 4, and mask those keys before the exponent).
  * lse includes the bias and the backward recomputes P with it; no gradient with respect to
  * key_bias is produced (sizes come from the non-differentiable match). Rejected
  * (MMT_ERR_INVALID, nothing launched): key_bias with wsum, and key_bias with the T5 `bias`.

@@ -44,6 +44,7 @@ SIGNATURES: dict[str, list] = {
     "mmt_topk_scatter_bwd": [P, I, I, I, I, L, L, P, I, P, L, L, P],
     "mmt_gemm_set_variant": [I],
     "mmt_gemm_last_route": [],
+    "mmt_attn_last_route": [],
     "mmt_set_deterministic": [P, P, L],
     "mmt_det_flush": [P, P, L, P],
     "mmt_gemm_colsum_rows": [I, I, I, I, I, I, I],
@@ -115,6 +116,7 @@ _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)
             "mmt_gemm_colsum_rows": I,    # returns a row count
             "mmt_gemm_last_route": I,     # returns a ROUTE_* value
+            "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -201,6 +203,22 @@ def route_ntw(bn: int, mt: int) -> int:
 
 def last_route() -> int:
     return call("mmt_gemm_last_route")
+
+
+# MMT_ATTN_ROUTE_* (include/mmt_api.h): what mmt_attn_last_route() reports
+(ATTN_ROUTE_NONE, ATTN_ROUTE_FWD_TILED_1W, ATTN_ROUTE_FWD_TILED_4W, ATTN_ROUTE_FWD_RES_ONEPASS,
+ ATTN_ROUTE_FWD_RES_TWOPASS, ATTN_ROUTE_BWD_TILED, ATTN_ROUTE_BWD_RES, ATTN_ROUTE_BWD_RES8) = range(8)
+ATTN_ROUTE_KERNEL_MASK, ATTN_ROUTE_WORKLIST = 0xff, 0x10000
+
+
+def attn_route(kernel: int, param: int, dh: int = 0, worklist: bool = False) -> int:
+    """The route of `kernel` with MMT_ATTN_ROUTE_PARAM `param` (the tiled forward's NQ, a resident
+    kernel's NTILE, the tiled backward's waves per workgroup) and, for the tiled kernels, Dh."""
+    return kernel | param << 8 | (dh // 64) << 12 | (ATTN_ROUTE_WORKLIST if worklist else 0)
+
+
+def attn_last_route() -> int:
+    return call("mmt_attn_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

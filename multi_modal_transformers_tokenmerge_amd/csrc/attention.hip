@@ -1259,6 +1259,9 @@ __global__ __launch_bounds__(64 * RES_NW, 2) void attn_bwd_res_kernel(
           for (int r = 0; r < 16; ++r) {
             const int mk = bitmask_of(w, rbit(r));
             sacc[r] = __int_as_float((__float_as_int(sacc[r]) & mk) | (~mk & (int)0xff800000u));
+            // a masked key's bias must not reach the exponent: the padding [L, roundup(L, 64)) of
+            // a key_bias row is unspecified (mmt_api.h), and -inf c2 + NaN / +inf is NaN, not -inf
+            if constexpr (KB) kbt[r] = __int_as_float(__float_as_int(kbt[r]) & mk);
           }
         }
         floatx16 ds;
@@ -2350,6 +2353,7 @@ inline int bwd_threads(int L) {
 
 #define ATTN_BWD_LAUNCH2(DH_, NTT_, DR_, KB_)                                                     \
   do {                                                                                            \
+    g_attn_route = MMT_ATTN_ROUTE_BWD_TILED | (NTT_ / 64) << 8 | (DH_ / 64) << 12;                \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<DH_, NTT_, DR_, KB_>), grid, dim3(NTT_), 0, s, g, m,   \
                        drop_bits, lp, dscale, (const bf16_t*)dout, d_s_b, d_s_t, lse,             \
                        (const bf16_t*)o, o_s_b, o_s_t, delta, (bf16_t*)dqkv, dq_s_b, dq_s_t,      \
@@ -2391,6 +2395,24 @@ extern "C" int mmt_dropout_bits(const uint32_t* rng, uint32_t layer, uint32_t si
   return MMT_OK;
 }
 
+// the kernel of the last mmt_attn_fwd* / mmt_attn_bwd* launch (MMT_ATTN_ROUTE_*, include/mmt_api.h;
+// mmt_attn_last_route), set next to every launch below
+static int g_attn_route = MMT_ATTN_ROUTE_NONE;
+extern "C" int mmt_attn_last_route(void) { return g_attn_route; }
+
+// The operand rules of include/mmt_api.h shared by forward and backward: a bf16 operand of rows
+// `width` elements wide, moved as 16-B vectors.
+static int check_rows(const char* fn, const char* what, const void* p, int64_t s_b, int64_t s_t,
+                      int64_t width) {
+  MMT_CHECK_ARG(s_t % 8 == 0 && s_b % 8 == 0 && (uintptr_t)p % 16 == 0,
+                "%s: %s needs a 16-B aligned base and row / batch strides that are multiples of 8 "
+                "bf16 elements (16-B vector loads and stores; got %lld / %lld)", fn, what,
+                (long long)s_t, (long long)s_b);
+  MMT_CHECK_ARG(s_t >= width, "%s: the row stride of %s (%lld) is below its row width %lld", fn,
+                what, (long long)s_t, (long long)width);
+  return MMT_OK;
+}
+
 // key_bias layout of include/mmt_api.h (mmt_attn_fwd_keybias); NULL passes
 static int check_key_bias(const char* fn, const float* key_bias, int64_t kb_s_b, int L, float scale) {
   if (!key_bias) return MMT_OK;
@@ -2418,13 +2440,16 @@ extern "C" int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, i
                                     const uint32_t* drop_bits, float keep_prob, const float* bias,
                                     void* o, int64_t o_s_b, int64_t o_s_t, float* lse, float* wsum,
                                     const float* key_bias, int64_t kb_s_b, mmt_stream_t stream) {
+  g_attn_route = MMT_ATTN_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(qkv && o && lse, "mmt_attn_fwd: null pointer");
+  MMT_CHECK_ARG(Dh == 64 || Dh == 128 || Dh == 256,
+                "mmt_attn_fwd: head dim %d unsupported (64, 128, 256)", Dh);
   MMT_CHECK_ARG(!key_bias || (!wsum && !bias),
                 "mmt_attn_fwd: key_bias cannot be combined with wsum or the additive (H, L, L) bias");
   if (int kc = check_key_bias("mmt_attn_fwd", key_bias, kb_s_b, L, scale)) return kc;
   MMT_CHECK_ARG(B > 0 && L > 0 && H > 0 && L <= MAXL, "mmt_attn_fwd: bad shape (L <= %d)", MAXL);
-  MMT_CHECK_ARG(s_t % 8 == 0 && s_b % 8 == 0 && o_s_t % 4 == 0 && o_s_b % 4 == 0,
-                "mmt_attn_fwd: strides must keep 16-B rows");
+  if (int rc = check_rows("mmt_attn_fwd", "qkv", qkv, s_b, s_t, 3 * (int64_t)H * Dh)) return rc;
+  if (int rc = check_rows("mmt_attn_fwd", "o", o, o_s_b, o_s_t, (int64_t)H * Dh)) return rc;
   MMT_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "mmt_attn_fwd: keep_prob");
   MMT_CHECK_ARG(!bias || L % 4 == 0, "mmt_attn_fwd: the additive bias needs L %% 4 == 0 (float4 rows)");
   AttnMask m;
@@ -2466,6 +2491,7 @@ extern "C" int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, i
       else RES1(NT_, false, false, false);                 \
     }                                                      \
   } while (0)
+      g_attn_route = (one1 ? MMT_ATTN_ROUTE_FWD_RES_ONEPASS : MMT_ATTN_ROUTE_FWD_RES_TWOPASS) | ntile << 8;
       switch (ntile) {
         case 2: RES2(2); break;
         case 4: RES2(4); break;
@@ -2491,15 +2517,18 @@ extern "C" int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, i
     if constexpr (DH_ <= 64 && NQ_ == 1) {                                                        \
       if (L <= 32) { /* one 32-row block (the T5 text): one-wave workgroups */                    \
         one_wave = true;                                                                          \
+        g_attn_route = MMT_ATTN_ROUTE_FWD_TILED_1W | NQ_ << 8 | (DH_ / 64) << 12;                 \
         hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_, 1, KB_>), dim3(1, H, B),          \
                            dim3(64), 0, as_stream(stream), g, m, drop_bits, lp, dscale, bias,     \
                            (bf16_t*)o, o_s_b, o_s_t, lse, wsum, key_bias, kb_s_b);                \
       }                                                                                           \
     }                                                                                             \
-    if (!one_wave)                                                                                \
+    if (!one_wave) {                                                                              \
+      g_attn_route = MMT_ATTN_ROUTE_FWD_TILED_4W | NQ_ << 8 | (DH_ / 64) << 12;                   \
       hipLaunchKernelGGL((attn_fwd_kernel<DH_, NQ_, WS_, DR_, 4, KB_>), grid, dim3(NT), 0,        \
                          as_stream(stream), g, m, drop_bits, lp, dscale, bias, (bf16_t*)o, o_s_b,  \
                          o_s_t, lse, wsum, key_bias, kb_s_b);                                     \
+    }                                                                                             \
   } while (0)
 #define FWD(DH_, NQ_)                                          \
   do {                                                         \
@@ -2549,11 +2578,16 @@ extern "C" int mmt_attn_bwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, i
                                     const float* lse, float* delta, void* dqkv, int64_t dq_s_b,
                                     int64_t dq_s_t, float* bias_grad, const float* key_bias,
                                     int64_t kb_s_b, mmt_stream_t stream) {
+  g_attn_route = MMT_ATTN_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(qkv && o && dout && lse && delta && dqkv, "mmt_attn_bwd: null pointer");
+  MMT_CHECK_ARG(Dh == 64 || Dh == 128 || Dh == 256,
+                "mmt_attn_bwd: head dim %d unsupported (64, 128, 256)", Dh);
   if (int kc = check_key_bias("mmt_attn_bwd", key_bias, kb_s_b, L, scale)) return kc;
   MMT_CHECK_ARG(B > 0 && L > 0 && H > 0 && L <= MAXL, "mmt_attn_bwd: bad shape");
-  MMT_CHECK_ARG(s_t % 8 == 0 && d_s_t % 8 == 0 && dq_s_t % 4 == 0 && o_s_t % 8 == 0,
-                "mmt_attn_bwd: strides must keep 16-B rows");
+  if (int rc = check_rows("mmt_attn_bwd", "qkv", qkv, s_b, s_t, 3 * (int64_t)H * Dh)) return rc;
+  if (int rc = check_rows("mmt_attn_bwd", "o", o, o_s_b, o_s_t, (int64_t)H * Dh)) return rc;
+  if (int rc = check_rows("mmt_attn_bwd", "dout", dout, d_s_b, d_s_t, (int64_t)H * Dh)) return rc;
+  if (int rc = check_rows("mmt_attn_bwd", "dqkv", dqkv, dq_s_b, dq_s_t, 3 * (int64_t)H * Dh)) return rc;
   MMT_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "mmt_attn_bwd: keep_prob");
   MMT_CHECK_ARG(!drop_bits == !drop_bits_t,
                 "mmt_attn_bwd: dropout needs both the mask and its transpose (mmt_dropout_bits)");
@@ -2606,6 +2640,8 @@ extern "C" int mmt_attn_bwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, i
     if (drop_bits) RESB1(NT_, true); \
     else RESB1(NT_, false);          \
   } while (0)
+      g_attn_route = (bwd8 ? MMT_ATTN_ROUTE_BWD_RES8 : MMT_ATTN_ROUTE_BWD_RES) | ntile << 8 |
+                     (plan.n_items > 0 ? MMT_ATTN_ROUTE_WORKLIST : 0);
       switch (ntile) {
         case 2: RESB2(2); break;
         case 4: RESB2(4); break;

@@ -291,6 +291,21 @@ def test_seqnorm_dropout_bwd_fused(dev, B, L, D, drop):
         torch.testing.assert_close(grads[i + 3], grads[i], rtol=1e-5, atol=1e-4)
 
 
+def _attn_routes(L):
+    """mmt_attn_last_route() of the Dh 64, 32 < L <= 320 launches: {"1": (forward, backward) of
+    the resident kernels (one-pass forward; concurrent phases up to L = 312, with the work list at
+    192 < L <= 256, the two-phase kernel beyond), "0": of the tiled kernels}."""
+    from multi_modal_transformers_tokenmerge_amd import _C
+    ntile = 2 * ((L + 63) // 64)
+    bwd = (_C.attn_route(_C.ATTN_ROUTE_BWD_RES8, ntile, worklist=192 < L <= 256) if L <= 312
+           else _C.attn_route(_C.ATTN_ROUTE_BWD_RES, ntile))
+    f64, f128 = L / (-(-L // 64) * 64), L / (-(-L // 128) * 128)
+    waves = 2 if f64 > f128 + 0.10 else 4
+    return {"1": (_C.attn_route(_C.ATTN_ROUTE_FWD_RES_ONEPASS, ntile), bwd),
+            "0": (_C.attn_route(_C.ATTN_ROUTE_FWD_TILED_4W, 2 if L <= 256 else 1, 64),
+                  _C.attn_route(_C.ATTN_ROUTE_BWD_TILED, waves, 64))}
+
+
 @pytest.mark.parametrize("B,L,H,mode,drop", [
     (2, 33, 3, "none", True), (2, 64, 2, "none", False), (3, 65, 2, "octo", True),
     (2, 101, 3, "causal", True), (2, 212, 6, "octo", True), (2, 292, 6, "octo", False),
@@ -299,8 +314,11 @@ def test_resident_attention_vs_tiled_and_torch(dev, B, L, H, mode, drop, monkeyp
     """The K/V-resident kernels (Dh 64, 32 < L <= 320: one workgroup per (sample, head), forward
     online softmax, two-phase backward with in-kernel bias column sums) against the tiled ones
     (MMT_ATTN_RES / MMT_ATTN_RES_BWD = 0) and against fp32 torch, on ragged L (odd, not a multiple
-    of 4 or 32), causal sets and dropout."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    of 4 or 32), causal sets and dropout. The route of every launch is asserted: resident one-pass
+    forward with NTILE = 2 ceil(L / 64) and the concurrent-phase backward (L = 320: the two-phase
+    kernel, the concurrent-phase LDS image ends at L = 312) against the four-wave tiled forward
+    (NQ = 2 up to L = 256, else 1) and the tiled backward at bwd_threads' workgroup size."""
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
     Dh = 64
     g = torch.Generator().manual_seed(L * 13 + H)
     qkv = torch.randn((B, L, 3 * H * Dh), generator=g).bfloat16().to(dev)
@@ -327,8 +345,10 @@ def test_resident_attention_vs_tiled_and_torch(dev, B, L, H, mode, drop, monkeyp
         monkeypatch.setenv("MMT_ATTN_RES", res)
         monkeypatch.setenv("MMT_ATTN_RES_BWD", res)
         o, lse = K.attn_fwd(qkv, H, scale, table, bits, kp)
+        assert _C.attn_last_route() == _attn_routes(L)[res][0]
         bg = torch.zeros(3 * H * Dh, device=dev)
         dq = K.attn_bwd(qkv, o, dout, lse, H, scale, table, bits, kp, bias_grad=bg)
+        assert _C.attn_last_route() == _attn_routes(L)[res][1]
         torch.cuda.synchronize()
         outs[res] = (o.float(), lse, dq.float(), bg)
     (o1, l1, d1, b1), (o0, l0, d0, b0) = outs["1"], outs["0"]
@@ -354,8 +374,11 @@ def test_resident_backward_concurrent_phases_bit_identical(dev, B, L, H, mode, d
     """The 8-wave resident backward (K, V, Q, dO all in LDS, phase A on waves 0-3 and phase B on
     waves 4-7 at the same time; the default) against the two-phase 4-wave kernel
     (MMT_ATTN_BWD8=0): the same arithmetic in the same order, so dQ / dK / dV agree bit for bit
-    (the bias gradient, one fp32 atomic per workgroup, to summation order)."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    (the bias gradient, one fp32 atomic per workgroup, to summation order). The route under each
+    setting is asserted. L = 312 is the largest length whose LDS image the concurrent-phase kernel
+    holds; the L = 320 case is the LDS fallback: the two-phase kernel under both settings, so there
+    the comparison is that kernel against itself (a rerun check)."""
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
     Dh = 64
     g = torch.Generator().manual_seed(L * 7 + H)
     qkv = torch.randn((B, L, 3 * H * Dh), generator=g).bfloat16().to(dev)
@@ -380,6 +403,9 @@ def test_resident_backward_concurrent_phases_bit_identical(dev, B, L, H, mode, d
         monkeypatch.setenv("MMT_ATTN_BWD8", v)
         bg = torch.zeros(3 * H * Dh, device=dev)
         dq = K.attn_bwd(qkv, o, dout, lse, H, scale, table, bits, kp, bias_grad=bg)
+        two_phase = _C.attn_route(_C.ATTN_ROUTE_BWD_RES, 2 * ((L + 63) // 64))
+        assert _C.attn_last_route() == (_attn_routes(L)["1"][1] if v == "1" else two_phase)
+        assert (_C.attn_last_route() == two_phase) == (v == "0" or L > 312)
         torch.cuda.synchronize()
         outs[v] = (dq, bg)
     assert torch.equal(outs["1"][0], outs["0"][0])
@@ -394,8 +420,9 @@ def test_onepass_forward_within_bf16_tolerance(dev, B, L, H, mode, drop, spread,
     (online softmax, lazy rescale at 2^8) against MMT_ATTN_ONEPASS=0 (the two-pass form): O within the bf16 bar of SURVEY §8c (rel 2e-2; asserted at 1e-2) of an
     fp32 torch reference on the same bf16 q / k / v, no worse than 1.5x the two-pass kernel's own
     error, and lse within 1e-4 of it — also with logits spread wide (`spread` scales q: running
-    maxima that move by many 2^8 steps, rows whose max sits in a late tile)."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    maxima that move by many 2^8 steps, rows whose max sits in a late tile). The route of each
+    launch is asserted (the one-pass / two-pass resident forward)."""
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
     Dh = 64
     g = torch.Generator().manual_seed(L * 5 + H)
     x = torch.randn((B, L, 3 * H * Dh), generator=g)
@@ -422,6 +449,9 @@ def test_onepass_forward_within_bf16_tolerance(dev, B, L, H, mode, drop, spread,
     for v in ("1", "0"):
         monkeypatch.setenv("MMT_ATTN_ONEPASS", v)
         o, lse = K.attn_fwd(qkv, H, scale, table, bits, kp)
+        assert _C.attn_last_route() == _C.attn_route(
+            _C.ATTN_ROUTE_FWD_RES_ONEPASS if v == "1" else _C.ATTN_ROUTE_FWD_RES_TWOPASS,
+            2 * ((L + 63) // 64))
         torch.cuda.synchronize()
         outs[v] = (o.float(), lse)
     ref = ref_attention(qkv.float(), H, scale, mask, keep, kp)

@@ -96,10 +96,36 @@ def make_bias(K, B, L, rng_set, dev, g, kind="sizes"):
     return kb.to(dev)
 
 
+def expected_routes(L, Dh):
+    """mmt_attn_last_route() of a key-bias forward and backward as the environment stands: the
+    resident forward (one-pass unless MMT_ATTN_ONEPASS=0) and, whatever MMT_ATTN_BWD8 says, the
+    two-phase resident backward (the concurrent-phase kernel has no key-bias form); else the tiled
+    forward (one wave at L <= 32; NQ = 2 up to L = 256 and past 320, Dh 64) and tiled backward."""
+    import os
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    ntile = 2 * ((L + 63) // 64)
+    if K.attn_fwd_resident(L, Dh):
+        one = os.environ.get("MMT_ATTN_ONEPASS", "1") != "0"
+        fwd = _C.attn_route(_C.ATTN_ROUTE_FWD_RES_ONEPASS if one else _C.ATTN_ROUTE_FWD_RES_TWOPASS, ntile)
+    elif Dh == 64 and L <= 32:
+        fwd = _C.attn_route(_C.ATTN_ROUTE_FWD_TILED_1W, 1, 64)
+    else:
+        nq = 2 if Dh == 64 and (L <= 256 or L > 320) else 1
+        fwd = _C.attn_route(_C.ATTN_ROUTE_FWD_TILED_4W, nq, Dh)
+    if K.attn_bwd_resident(L, Dh):
+        bwd = _C.attn_route(_C.ATTN_ROUTE_BWD_RES, ntile)
+    else:
+        f64, f128 = L / (-(-L // 64) * 64), L / (-(-L // 128) * 128)
+        bwd = _C.attn_route(_C.ATTN_ROUTE_BWD_TILED, 2 if f64 > f128 + 0.10 else 4, Dh)
+    return fwd, bwd
+
+
 def run_case(dev, L, H, Dh, mode, drop, kind="sizes", B=2):
     """One forward + backward with a key bias. Returns (o, lse, dqkv, bgrad - 0.5) of the kernels
-    and (o, lse, dqkv) of the torch reference."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    and (o, lse, dqkv) of the torch reference. Asserts the route of both launches
+    (expected_routes)."""
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    want_fwd, want_bwd = expected_routes(L, Dh)
     g = torch.Generator().manual_seed(L * 7 + H + Dh)
     qkv = torch.randn((B, L, 3 * H * Dh), generator=g).bfloat16().to(dev)
     dout = torch.randn((B, L, H * Dh), generator=g).bfloat16().to(dev)
@@ -111,8 +137,10 @@ def run_case(dev, L, H, Dh, mode, drop, kind="sizes", B=2):
     bits = K.dropout_bits(rng, 1, 2, L, L, kp) if drop else None
     keep = bits_to_keep(bits, L).to(dev) if drop else None
     o, lse = K.attn_fwd(qkv, H, scale, table, bits, kp, key_bias=kb)
+    assert _C.attn_last_route() == want_fwd, hex(_C.attn_last_route())
     bg = torch.full((3 * H * Dh,), 0.5, device=dev)
     dq = K.attn_bwd(qkv, o, dout, lse, H, scale, table, bits, kp, bias_grad=bg, key_bias=kb)
+    assert _C.attn_last_route() == want_bwd, hex(_C.attn_last_route())
     torch.cuda.synchronize()
     K.device_status()
     qf = qkv.float().requires_grad_()
@@ -143,7 +171,8 @@ def check_vs_torch(got, ref, B, L):
     (65, 3, "octo", True, {"MMT_ATTN_ONEPASS": "0"}),
     (292, 6, "octo", False, {"MMT_ATTN_BWD8": "0"})])
 def test_resident_path_vs_torch(dev, L, H, mode, drop, env, monkeypatch):
-    """Resident forward (one-pass and exact-max forms) and the two-phase resident backward."""
+    """Resident forward (one-pass and exact-max forms) and the two-phase resident backward, which
+    a key bias takes under either setting of MMT_ATTN_BWD8 (routes asserted in run_case)."""
     from multi_modal_transformers_tokenmerge_amd import _kernels as K
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -158,6 +187,8 @@ def test_resident_path_vs_torch(dev, L, H, mode, drop, env, monkeypatch):
     (200, 2, 128, "octo", True),
     (70, 2, 256, "octo", False)])
 def test_tiled_path_vs_torch(dev, L, H, Dh, mode, drop):
+    """The tiled kernels (routes asserted in run_case): one wave at L = 20, four waves with
+    NQ = 2 at L = 330 and NQ = 1 at Dh 128 / 256."""
     from multi_modal_transformers_tokenmerge_amd import _kernels as K
     assert not K.attn_fwd_resident(L, Dh) and not K.attn_bwd_resident(L, Dh)
     got, ref = run_case(dev, L, H, Dh, mode, drop)
