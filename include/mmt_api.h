@@ -800,6 +800,49 @@ int mmt_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow_bf1
                   const int32_t* state, const float* opt, double b1, double b2, double eps,
                   double wd, mmt_stream_t stream);
 
+/* Parameter groups: optax.multi_transform({"trainable": optax.chain(clip_by_global_norm,
+ * adamw(schedule, mask = decay_mask)), "frozen": set_to_zero()}) over the same flat buffer.
+ *
+ * chunk_flags: one byte per MMT_GROUP_CHUNK = 64 consecutive elements of the flat buffer,
+ * ceil(n / 64) bytes on the device, bit 0 (MMT_GROUP_NO_DECAY) = the chunk takes no weight
+ * decay, bit 1 (MMT_GROUP_FROZEN) = the chunk is never updated; the other bits are ignored.
+ * The caller aligns every parameter to 64 elements, so a chunk never straddles two parameters
+ * and a 16-B vector never straddles two chunks. `chunk` must be MMT_GROUP_CHUNK and chunk_flags
+ * non-null: anything else returns MMT_ERR_INVALID before a launch.
+ *
+ * mmt_adamw_groups covers both forms above: opt == NULL takes lr and grad_scale from the host
+ * arguments (mmt_adamw); opt != NULL reads lr = opt[3], the gradient factor opt[2] and the skip
+ * flag opt[6] (mmt_adamw_dev; lr and grad_scale are ignored, opt[6] != 0 returns at once and
+ * nothing is touched). It has the geometry of the plain kernels (a wave covers one chunk per
+ * iteration) and calls the same per-element update function, so
+ *   - a chunk with no bit set is bit-identical to mmt_adamw / mmt_adamw_dev on the same values;
+ *   - a NO_DECAY chunk is bit-identical to the plain kernel called with wd = 0;
+ *   - a FROZEN chunk issues no load or store of p, g, m, v or the shadow: those bytes stay as
+ *     they are whatever g holds there (NaN and Inf included).
+ *
+ * mmt_optim_prepare_groups is mmt_optim_prepare over the trainable chunks: the same two
+ * launches, the same partition (workgroup b owns the same 16-B vectors of g), the same
+ * accumulators and trees. A vector of a FROZEN chunk is not loaded and enters as zeros, so it
+ * contributes nothing to sum g^2 (opt[0] is the norm of the trainable gradient) nor to the
+ * non-finite flag; every workgroup still stores its partial, 0 for an empty or all-frozen
+ * range. With no FROZEN bit set the eight opt words are bit-identical to mmt_optim_prepare's.
+ * Skipped vectors only shorten a chain, so the bound ceil(per / 1024) + 13 holds, and the
+ * result is bitwise reproducible. All chunks frozen: sum g^2 = 0, grad_norm 0, clip 1,
+ * gmul = grad_scale (no division takes place). NO_DECAY does not matter here. */
+#define MMT_GROUP_CHUNK 64
+#define MMT_GROUP_CHUNK_SHIFT 6
+#define MMT_GROUP_NO_DECAY 1
+#define MMT_GROUP_FROZEN 2
+int mmt_adamw_groups(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n,
+                     const int32_t* state, const float* opt, double lr, double b1, double b2,
+                     double eps, double wd, float grad_scale, const uint8_t* chunk_flags,
+                     int chunk, mmt_stream_t stream);
+int mmt_optim_prepare_groups(const float* g, int64_t n, float grad_scale, double max_norm,
+                             int skip_nonfinite, const mmt_lr_schedule_t* sched,
+                             const int32_t* state, float* opt, void* workspace,
+                             int64_t ws_bytes, const uint8_t* chunk_flags, int chunk,
+                             mmt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ class CategoricalActionHead:
     def __init__(self, store: ParamStore, name: str, embedding_dim: int, action_dim: int,
                  num_bins: int, max_action: float):
         self.D, self.A, self.num_bins, self.max_action = embedding_dim, action_dim, num_bins, float(max_action)
+        self.name = name  # the prefix of the head's parameters in the store
         self.dense = Dense(store, f"{name}/Dense_0", embedding_dim, num_bins)
         self._edges = {}
 

@@ -20,6 +20,7 @@ class ContinuousActionHead:
     def __init__(self, store: ParamStore, name: str, embedding_dim: int, action_dim: int,
                  max_action: float):
         self.D, self.A, self.max_action = embedding_dim, action_dim, float(max_action)
+        self.name = name  # the prefix of the head's parameters in the store
         self.dense = Dense(store, f"{name}/Dense_0", embedding_dim, action_dim)
 
     def forward(self, readout_mean: torch.Tensor) -> torch.Tensor:

@@ -323,10 +323,13 @@ class MultiHeadAttentionPooling(Bindable):
         return out, dict(B=B, n=n, r=r, kv=kv, q=q, ctx=ctx, p=p, a=a, y=y, mu=mu, rs=rs, h=h)
 
     # ----------------------------------------------------------------------------- backward
-    def backward(self, de: torch.Tensor, sv: dict, row_flag: torch.Tensor) -> torch.Tensor:
+    def backward(self, de: torch.Tensor, sv: dict, row_flag: torch.Tensor,
+                 need_dx: bool = True) -> torch.Tensor | None:
         """de (B, D) bf16 (any row stride): the gradient of the pooled embedding. row_flag (L,)
         int32: the slot index of every pooled row of the sequence, -1 elsewhere. Accumulates every
-        parameter gradient and returns the whole dx (B, L, D) fp32 (zero outside the pooled rows)."""
+        parameter gradient and returns the whole dx (B, L, D) fp32 (zero outside the pooled rows);
+        need_dx False (nothing below the module is trained): the module's own parameter
+        gradients only, returns None."""
         B, n, D = sv["B"], sv["n"], self.D
         h, a = sv["h"], sv["a"]
         dz1 = self.mlp.dense_out.bwd(de, h, gate=h, gate_scale=1.0)   # relu backward in the epilogue
@@ -344,7 +347,9 @@ class MultiHeadAttentionPooling(Bindable):
         _, _, dqb = K.attn_pool_bwd(dctx, sv["p"], sv["q"], kv[:, :D], kv[:, D:],
                                     dk=dkv[:, :D], dv=dkv[:, D:])
         self._query_backward(dqb)
-        dr = self.kv.bwd(dkv, sv["r"])
+        dr = self.kv.bwd(dkv, sv["r"], need_dx=need_dx)
+        if not need_dx:
+            return None
         return K.rows_scatter_bwd(dr.view(B, n, D), row_flag)
 
     def _query_backward(self, dqb: torch.Tensor):
@@ -809,15 +814,20 @@ class StackedEncoder1DBlock(Bindable):
             saved[-1]["merge_source"] = {si: (buf, final_t[si]) for si, buf in sources.items()}
         return x, saved
 
-    def backward(self, dx, saved, ctxs, lo: int = 0, hi: int | None = None):
+    def backward(self, dx, saved, ctxs, lo: int = 0, hi: int | None = None, dz=None,
+                 floor: int | None = None):
         """Backward through blocks hi-1 .. lo (all by default); a staged backward (gradient
-        all-reduce overlapped with the remaining blocks) calls it in several ranges."""
+        all-reduce overlapped with the remaining blocks) calls it in several ranges. floor (a
+        range of a longer backward that goes down to block `floor`): block lo also produces block
+        lo-1's MLP-output dropout backward when lo-1 >= floor, as it does inside a range, and the
+        call returns (dx, dz) for the next range to pass back in as `dz`: the ranges then launch
+        what the single backward launches. floor None: the range stands alone, returns dx."""
         hi = len(self.blocks) if hi is None else hi
-        dz = None
+        low = lo if floor is None else floor
         for i in range(hi - 1, lo - 1, -1):
             # block i's LayerNorm_0 backward also does block i-1's MLP-output dropout backward
-            prev = (self.blocks[i - 1], saved[i - 1], ctxs[i - 1]) if i - 1 >= lo else None
+            prev = (self.blocks[i - 1], saved[i - 1], ctxs[i - 1]) if i - 1 >= low else None
             with phase(f"bwd/block{i}"):
                 dx, dz = self.blocks[i].backward(dx, saved[i], ctxs[i], dz2=dz, prev=prev)
             wgrad_overlap.block_done()
-        return dx
+        return dx if floor is None else (dx, dz)

@@ -528,35 +528,54 @@ __global__ void embedding_gather_kernel(const int32_t* __restrict__ ids, int64_t
   *reinterpret_cast<uint4*>(out + r * D + c) = *reinterpret_cast<const uint4*>(table + (int64_t)id * D + c);
 }
 
-// AdamW (optax.adamw semantics, decoupled weight decay on every parameter, bias-corrected
-// moments) over the flat fp32 master buffer; writes the bf16 shadow used by the GEMMs.
+// AdamW (optax.adamw semantics, decoupled weight decay on every parameter unless a group table
+// says otherwise: adamw_groups_kernel; bias-corrected moments) over the flat fp32 master buffer; writes the bf16 shadow used by the GEMMs.
 // One update function for both kernels below, so their arithmetic is the same instructions.
 // The grid-stride bounds come from the kernels: blockDim / gridDim read inside a kernel body
 // fold to the uniform-workgroup form, read in a device function they do not.
+struct AdamwCoef {
+  float b1, b2, bc1, bc2, omb1, omb2;
+};
+
+__device__ __forceinline__ AdamwCoef adamw_coef(double b1d, double b2d, const int step) {
+  // the betas arrive in double (optax / torch hold them as Python floats): 1 - b and the bias
+  // corrections are formed in double and rounded once (fp32 1.f - 0.999f would differ from
+  // (float)0.001 by 1.3e-5 relative)
+  AdamwCoef c;
+  c.b1 = (float)b1d;
+  c.b2 = (float)b2d;
+  c.bc1 = (float)(1.0 - pow(b1d, (double)step));
+  c.bc2 = (float)(1.0 - pow(b2d, (double)step));
+  c.omb1 = (float)(1.0 - b1d);
+  c.omb2 = (float)(1.0 - b2d);
+  return c;
+}
+
+// One element's update: the only place the arithmetic is written, shared by every AdamW kernel.
+__device__ __forceinline__ void adamw_elem(float* __restrict__ p, const float* __restrict__ g,
+                                           float* __restrict__ m, float* __restrict__ v,
+                                           bf16_t* __restrict__ shadow, const int64_t i,
+                                           const AdamwCoef& c, float lr, float eps, float wd,
+                                           float grad_scale) {
+  const float gi = g[i] * grad_scale;
+  const float mi = c.b1 * m[i] + c.omb1 * gi;
+  const float vi = c.b2 * v[i] + c.omb2 * (gi * gi);
+  m[i] = mi;
+  v[i] = vi;
+  const float upd = (mi / c.bc1) / (sqrtf(vi / c.bc2) + eps) + wd * p[i];
+  const float pn = p[i] - lr * upd;
+  p[i] = pn;
+  if (shadow) shadow[i] = f2bf(pn);
+}
+
 __device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g,
                                              float* __restrict__ m, float* __restrict__ v,
                                              bf16_t* __restrict__ shadow, int64_t n,
                                              const int step, float lr,
                                              double b1d, double b2d, float eps, float wd,
                                              float grad_scale, int64_t first, int64_t stride) {
-  // the betas arrive in double (optax / torch hold them as Python floats): 1 - b and the bias
-  // corrections are formed in double and rounded once (fp32 1.f - 0.999f would differ from
-  // (float)0.001 by 1.3e-5 relative)
-  const float b1 = (float)b1d, b2 = (float)b2d;
-  const float bc1 = (float)(1.0 - pow(b1d, (double)step));
-  const float bc2 = (float)(1.0 - pow(b2d, (double)step));
-  const float omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
-  for (int64_t i = first; i < n; i += stride) {
-    const float gi = g[i] * grad_scale;
-    const float mi = b1 * m[i] + omb1 * gi;
-    const float vi = b2 * v[i] + omb2 * (gi * gi);
-    m[i] = mi;
-    v[i] = vi;
-    const float upd = (mi / bc1) / (sqrtf(vi / bc2) + eps) + wd * p[i];
-    const float pn = p[i] - lr * upd;
-    p[i] = pn;
-    if (shadow) shadow[i] = f2bf(pn);
-  }
+  const AdamwCoef c = adamw_coef(b1d, b2d, step);
+  for (int64_t i = first; i < n; i += stride) adamw_elem(p, g, m, v, shadow, i, c, lr, eps, wd, grad_scale);
 }
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -583,6 +602,64 @@ __global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict_
   if (skip != 0.f) return;
   adamw_update(p, g, m, v, shadow, n, step, lr, b1d, b2d, eps, wd, gmul,
                (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// AdamW with parameter groups (optax.adamw(mask=...) inside optax.multi_transform with
+// set_to_zero for the frozen group): one flag byte per 64-element chunk of the flat buffer,
+// bit 0 = no weight decay, bit 1 = frozen (include/mmt_api.h MMT_GROUP_*). The launch geometry is
+// the plain kernels': 256 lanes and a grid stride that is a multiple of 64, so in every
+// iteration a wave covers exactly one chunk and its flag is wave-uniform. A wave fetches the
+// flags of its next 64 iterations with one load (lane k holds iteration k's), turns them into two
+// 64-bit scalar masks by ballot, and the loop branches on their bits: no memory wait stands
+// between one iteration's stores and the next one's loads, as in the plain loop. (A flag load inside the loop made the compiler
+// wait for every outstanding vector memory operation, the stores included, at the loop's head:
+// +16 % at 22.5 M elements.) A frozen chunk is skipped before any load of p, g, m, v or the
+// shadow; an undecayed one runs adamw_elem with wd = 0.
+// DEV: lr, the gradient factor and the skip flag come from the opt words, as adamw_dev_kernel.
+template <bool DEV>
+__global__ void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                    float* __restrict__ m, float* __restrict__ v,
+                                    bf16_t* __restrict__ shadow, int64_t n,
+                                    const int32_t* __restrict__ state,
+                                    const float* __restrict__ opt, float lr_host, double b1d,
+                                    double b2d, float eps, float wd, float gs_host,
+                                    const uint8_t* __restrict__ flags) {
+  float lr = lr_host, gmul = gs_host;
+  int step;
+  if (DEV) {
+    const float skip = opt[6];
+    lr = opt[3];
+    gmul = opt[2];
+    step = state[1] + 1;
+    asm volatile("" ::"s"(skip), "s"(lr), "s"(gmul), "s"(step));
+    if (skip != 0.f) return;
+  } else {
+    step = state[1] + 1;
+  }
+  const AdamwCoef c = adamw_coef(b1d, b2d, step);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const int64_t nc = (n + MMT_GROUP_CHUNK - 1) >> MMT_GROUP_CHUNK_SHIFT;  // chunks; < 2^31
+  // the wave's first chunk and its chunk stride, as scalars (the host bounds the grid, so a
+  // chunk index fits an int)
+  const int64_t c0 = __builtin_amdgcn_readfirstlane((int)((first - lane) >> MMT_GROUP_CHUNK_SHIFT));
+  const int64_t cs = stride >> MMT_GROUP_CHUNK_SHIFT;
+  for (int64_t k0 = 0; c0 + k0 * cs < nc; k0 += 64) {
+    const int64_t cl = c0 + (k0 + lane) * cs;  // lane k fetches the flag of iteration k0 + k
+    const unsigned fv = cl < nc ? flags[cl] : (unsigned)MMT_GROUP_FROZEN;
+    // two 64-bit scalar masks, bit k = iteration k0 + k: the loop below depends on no register
+    // a load wrote
+    const uint64_t frozen = __ballot((fv & MMT_GROUP_FROZEN) != 0);
+    const uint64_t no_decay = __ballot((fv & MMT_GROUP_NO_DECAY) != 0);
+    for (int k = 0; k < 64; ++k) {
+      if (c0 + (k0 + k) * cs >= nc) break;
+      if ((frozen >> k) & 1) continue;
+      const int64_t i = first + (k0 + k) * stride;
+      if (i < n)
+        adamw_elem(p, g, m, v, shadow, i, c, lr, eps, ((no_decay >> k) & 1) ? 0.f : wd, gmul);
+    }
+  }
 }
 
 // Sum of squares of the flat gradient, launch 1 of mmt_optim_prepare: GN_GRID workgroups (a
@@ -625,6 +702,58 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
   if (blockIdx.x == GN_GRID - 1 && (int64_t)threadIdx.x < (n & 3)) {
     const float t = g[4 * n4 + threadIdx.x];
     a0.x = fmaf(t, t, a0.x);
+  }
+  const float sx = (a0.x + a1.x) + (a2.x + a3.x), sy = (a0.y + a1.y) + (a2.y + a3.y);
+  const float sz = (a0.z + a1.z) + (a2.z + a3.z), sw = (a0.w + a1.w) + (a2.w + a3.w);
+  float s = (sx + sy) + (sz + sw);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// grad_sumsq_kernel over the trainable chunks only (launch 1 of mmt_optim_prepare_groups): the
+// same partition, the same accumulators and the same trees; a 16-B vector of a frozen chunk
+// (16 vectors per 64-element chunk, so a vector never straddles two) is not loaded and enters
+// as zeros, which leaves its accumulator's bits as they are (fma(0, 0, a) = a for a >= +0).
+// With no frozen bit set every partial is bit-identical to grad_sumsq_kernel's; chains only get
+// shorter otherwise.
+__device__ __forceinline__ float4 load_trainable(const float4* __restrict__ g4,
+                                                 const uint8_t* __restrict__ flags, int64_t i) {
+  if (flags[i >> (MMT_GROUP_CHUNK_SHIFT - 2)] & MMT_GROUP_FROZEN) return make_float4(0.f, 0.f, 0.f, 0.f);
+  return g4[i];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_groups_kernel(const float* __restrict__ g,
+                                                                int64_t n,
+                                                                const uint8_t* __restrict__ flags,
+                                                                float* __restrict__ partial) {
+  __shared__ float wsum[4];
+  const int64_t n4 = n >> 2;
+  const int64_t per = (n4 + GN_GRID - 1) / GN_GRID;
+  const int64_t lo = std::min<int64_t>((int64_t)blockIdx.x * per, n4);
+  const int64_t hi = std::min<int64_t>(lo + per, n4);
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+  int64_t i = lo + threadIdx.x;
+  for (; i + 768 < hi; i += 1024) {
+    const float4 x0 = load_trainable(g4, flags, i), x1 = load_trainable(g4, flags, i + 256);
+    const float4 x2 = load_trainable(g4, flags, i + 512), x3 = load_trainable(g4, flags, i + 768);
+    sumsq_acc(a0, x0);
+    sumsq_acc(a1, x1);
+    sumsq_acc(a2, x2);
+    sumsq_acc(a3, x3);
+  }
+  if (i < hi) sumsq_acc(a0, load_trainable(g4, flags, i));
+  if (i + 256 < hi) sumsq_acc(a1, load_trainable(g4, flags, i + 256));
+  if (i + 512 < hi) sumsq_acc(a2, load_trainable(g4, flags, i + 512));
+  if (blockIdx.x == GN_GRID - 1 && (int64_t)threadIdx.x < (n & 3)) {
+    const int64_t e = 4 * n4 + threadIdx.x;
+    if (!(flags[e >> MMT_GROUP_CHUNK_SHIFT] & MMT_GROUP_FROZEN)) {
+      const float t = g[e];
+      a0.x = fmaf(t, t, a0.x);
+    }
   }
   const float sx = (a0.x + a1.x) + (a2.x + a3.x), sy = (a0.y + a1.y) + (a2.y + a3.y);
   const float sz = (a0.z + a1.z) + (a2.z + a3.z), sw = (a0.w + a1.w) + (a2.w + a3.w);
@@ -992,42 +1121,70 @@ extern "C" int mmt_adamw(float* p, const float* g, float* m, float* v, void* sha
   return MMT_OK;
 }
 
-extern "C" int mmt_optim_prepare(const float* g, int64_t n, float grad_scale, double max_norm,
-                                 int skip_nonfinite, const mmt_lr_schedule_t* sched,
-                                 const int32_t* state, float* opt, void* workspace,
-                                 int64_t ws_bytes, mmt_stream_t stream) {
-  MMT_CHECK_ARG(g && sched && state && opt && workspace, "mmt_optim_prepare: null argument");
-  MMT_CHECK_ARG(n > 0, "mmt_optim_prepare: n = %lld", (long long)n);
+// Both prepare entry points: `who` names the caller in the messages, flags == nullptr is the
+// plain form.
+static int optim_prepare(const char* who, const float* g, int64_t n, float grad_scale,
+                         double max_norm, int skip_nonfinite, const mmt_lr_schedule_t* sched,
+                         const int32_t* state, float* opt, void* workspace, int64_t ws_bytes,
+                         const uint8_t* flags, mmt_stream_t stream) {
+  MMT_CHECK_ARG(g && sched && state && opt && workspace, "%s: null argument", who);
+  MMT_CHECK_ARG(n > 0, "%s: n = %lld", who, (long long)n);
   MMT_CHECK_ARG((reinterpret_cast<uintptr_t>(g) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(workspace) & 3) == 0,
-                "mmt_optim_prepare: g must be 16-B aligned (workspace 4-B)");
+                "%s: g must be 16-B aligned (workspace 4-B)", who);
   MMT_CHECK_ARG(ws_bytes >= mmt::grad_norm_workspace(n),
-                "mmt_optim_prepare: workspace %lld B < %lld B (mmt_workspace_size)",
+                "%s: workspace %lld B < %lld B (mmt_workspace_size)", who,
                 (long long)ws_bytes, (long long)mmt::grad_norm_workspace(n));
   const mmt_lr_schedule_t& sc = *sched;
   MMT_CHECK_ARG(sc.kind == MMT_SCHED_CONSTANT || sc.kind == MMT_SCHED_WARMUP_COSINE ||
                     sc.kind == MMT_SCHED_WARMUP_RSQRT,
-                "mmt_optim_prepare: unknown schedule kind %d", sc.kind);
+                "%s: unknown schedule kind %d", who, sc.kind);
   if (sc.kind != MMT_SCHED_CONSTANT)
-    MMT_CHECK_ARG(sc.warmup_steps >= 1, "mmt_optim_prepare: warmup_steps %lld < 1",
+    MMT_CHECK_ARG(sc.warmup_steps >= 1, "%s: warmup_steps %lld < 1", who,
                   (long long)sc.warmup_steps);
   if (sc.kind == MMT_SCHED_WARMUP_COSINE) {
-    MMT_CHECK_ARG(sc.peak_value != 0.0, "mmt_optim_prepare: cosine peak_value 0 (alpha = end / peak)");
+    MMT_CHECK_ARG(sc.peak_value != 0.0, "%s: cosine peak_value 0 (alpha = end / peak)", who);
     MMT_CHECK_ARG(sc.decay_steps > sc.warmup_steps,
-                  "mmt_optim_prepare: cosine decay_steps %lld <= warmup_steps %lld",
+                  "%s: cosine decay_steps %lld <= warmup_steps %lld", who,
                   (long long)sc.decay_steps, (long long)sc.warmup_steps);
   }
   if (sc.kind == MMT_SCHED_WARMUP_RSQRT)
-    MMT_CHECK_ARG(sc.timescale > 0.0, "mmt_optim_prepare: rsqrt timescale %g <= 0", sc.timescale);
+    MMT_CHECK_ARG(sc.timescale > 0.0, "%s: rsqrt timescale %g <= 0", who, sc.timescale);
   float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GN_GRID), dim3(256), 0, as_stream(stream), g, n,
-                     partial);
-  MMT_CHECK_LAUNCH("mmt_optim_prepare (partial sums)");
+  if (flags)
+    hipLaunchKernelGGL(grad_sumsq_groups_kernel, dim3(GN_GRID), dim3(256), 0, as_stream(stream),
+                       g, n, flags, partial);
+  else
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GN_GRID), dim3(256), 0, as_stream(stream), g, n,
+                       partial);
+  MMT_CHECK_LAUNCH(flags ? "mmt_optim_prepare_groups (partial sums)"
+                         : "mmt_optim_prepare (partial sums)");
   const OptimCtl ctl{sc, (double)grad_scale, max_norm, skip_nonfinite != 0};
   hipLaunchKernelGGL(optim_finalise_kernel, dim3(1), dim3(256), 0, as_stream(stream),
                      (const float*)partial, state, opt, ctl);
-  MMT_CHECK_LAUNCH("mmt_optim_prepare (finalise)");
+  MMT_CHECK_LAUNCH(flags ? "mmt_optim_prepare_groups (finalise)" : "mmt_optim_prepare (finalise)");
   return MMT_OK;
+}
+
+extern "C" int mmt_optim_prepare(const float* g, int64_t n, float grad_scale, double max_norm,
+                                 int skip_nonfinite, const mmt_lr_schedule_t* sched,
+                                 const int32_t* state, float* opt, void* workspace,
+                                 int64_t ws_bytes, mmt_stream_t stream) {
+  return optim_prepare("mmt_optim_prepare", g, n, grad_scale, max_norm, skip_nonfinite, sched,
+                       state, opt, workspace, ws_bytes, nullptr, stream);
+}
+
+extern "C" int mmt_optim_prepare_groups(const float* g, int64_t n, float grad_scale,
+                                        double max_norm, int skip_nonfinite,
+                                        const mmt_lr_schedule_t* sched, const int32_t* state,
+                                        float* opt, void* workspace, int64_t ws_bytes,
+                                        const uint8_t* chunk_flags, int chunk,
+                                        mmt_stream_t stream) {
+  MMT_CHECK_ARG(chunk_flags, "mmt_optim_prepare_groups: null chunk_flags");
+  MMT_CHECK_ARG(chunk == MMT_GROUP_CHUNK, "mmt_optim_prepare_groups: chunk %d != %d", chunk,
+                MMT_GROUP_CHUNK);
+  return optim_prepare("mmt_optim_prepare_groups", g, n, grad_scale, max_norm, skip_nonfinite,
+                       sched, state, opt, workspace, ws_bytes, chunk_flags, stream);
 }
 
 extern "C" int mmt_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow_bf16,
@@ -1038,6 +1195,28 @@ extern "C" int mmt_adamw_dev(float* p, const float* g, float* m, float* v, void*
   hipLaunchKernelGGL(adamw_dev_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), p, g, m, v,
                      (bf16_t*)shadow_bf16, n, state, opt, b1, b2, (float)eps, (float)wd);
   MMT_CHECK_LAUNCH("mmt_adamw_dev");
+  return MMT_OK;
+}
+
+extern "C" int mmt_adamw_groups(float* p, const float* g, float* m, float* v, void* shadow_bf16,
+                                int64_t n, const int32_t* state, const float* opt, double lr,
+                                double b1, double b2, double eps, double wd, float grad_scale,
+                                const uint8_t* chunk_flags, int chunk, mmt_stream_t stream) {
+  MMT_CHECK_ARG(p && g && m && v && state && n > 0, "mmt_adamw_groups: args");
+  MMT_CHECK_ARG(chunk_flags, "mmt_adamw_groups: null chunk_flags");
+  MMT_CHECK_ARG(chunk == MMT_GROUP_CHUNK, "mmt_adamw_groups: chunk %d != %d", chunk,
+                MMT_GROUP_CHUNK);
+  // the same geometry as mmt_adamw: 256 lanes, so a wave's 64 elements are one chunk
+  const int64_t blocks = std::min<int64_t>((n + 255) / 256, 256 * 8);
+  if (opt)
+    hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(blocks), dim3(256), 0, as_stream(stream), p,
+                       g, m, v, (bf16_t*)shadow_bf16, n, state, opt, 0.f, b1, b2, (float)eps,
+                       (float)wd, 0.f, chunk_flags);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(blocks), dim3(256), 0, as_stream(stream),
+                       p, g, m, v, (bf16_t*)shadow_bf16, n, state, opt, (float)lr, b1, b2,
+                       (float)eps, (float)wd, grad_scale, chunk_flags);
+  MMT_CHECK_LAUNCH("mmt_adamw_groups");
   return MMT_OK;
 }
 

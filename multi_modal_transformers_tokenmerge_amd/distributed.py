@@ -123,6 +123,7 @@ class DDPStep:
                              "(state.allreduce) so AdamW averages the summed gradients")
         self.loss_buf = torch.zeros(1, device=model.device)
         self.graphs = []
+        self._g_stage, self._g_opt = {}, None  # staged form: stage -> its graph; AdamW's graph
         self._st = {}
         self._sources = None
 
@@ -215,11 +216,25 @@ class DDPStep:
         m.backward_stage(self._st["st"], k, self.bounds)
         if self._t5_graphed_in and k == 0:  # joined inside the stage's graph (self-contained)
             torch.cuda.current_stream().wait_stream(self._t5_side)
-        if self._t5_graphed_in and k == self.S - 1:  # after the text projection's dW
+        # after the text projection's dW (the last stage that runs: it is skipped when frozen)
+        if self._t5_graphed_in and k == max(i for i, a in enumerate(self.active) if a):
             self.t5_cur.copy_(self.t5_nxt)
 
     def _opt(self):
         self.state.apply_gradients()
+
+    @property
+    def active(self):
+        """Per backward stage: does it launch anything (Octo.stage_active)? With frozen
+        parameters (AdamW.frozen_keys) a stage wholly below the backward's cut does not, and is
+        neither captured nor replayed."""
+        return [self.model.stage_active(k, self.bounds) for k in range(self.S)]
+
+    @property
+    def reduced(self):
+        """Per gradient region of the staged form: is it all-reduced? Not if its parameters are
+        all frozen: nothing reads that gradient."""
+        return [self.model.store.region_trainable(lo, hi) for lo, hi in self.regions]
 
     def merge_source(self):
         """{set index: MergeSource} of the last step (Octo.merge_source; needs
@@ -230,11 +245,20 @@ class DDPStep:
 
     @property
     def exposed_bytes(self) -> int:
-        """fp32 gradient bytes all-reduced after the backward's last stage (not overlapped)."""
+        """fp32 gradient bytes all-reduced after the backward's last stage (not overlapped): the
+        region of the last stage that launches anything, 0 if that region is all frozen (it is
+        not reduced, and the earlier regions' reductions run beside that stage)."""
         if not self.distributed:
             return 0
-        lo, hi = self.regions[-1] if self.regions else (0, self.model.store.n)
-        return 4 * (hi - lo)
+        if not self.regions:
+            return 4 * self.model.store.n
+        for k in reversed(range(self.S)):
+            if self.reduced[k]:
+                lo, hi = self.regions[k]
+                return 4 * (hi - lo)
+            if self.active[k]:
+                return 0
+        return 0
 
     def _reduce_async(self, k):
         lo, hi = self.regions[k]
@@ -306,8 +330,11 @@ class DDPStep:
             torch.cuda.current_stream().wait_stream(side)
         if self.S > 1:
             for k in range(self.S):   # one graph per backward stage (the first holds the forward)
-                cap(lambda k=k: self._stage(k))
+                if self.active[k]:
+                    cap(lambda k=k: self._stage(k))
+                    self._g_stage[k] = self.graphs[-1]
             cap(self._opt)
+            self._g_opt = self.graphs[-1]
         elif self.distributed:
             cap(self._fwd_bwd)
             cap(self._opt)
@@ -329,12 +356,14 @@ class DDPStep:
         if self.S > 1:
             works = []
             for k in range(self.S):
-                g[k].replay() if self.use_graph else self._stage(k)
-                works.append(self._reduce_async(k))
+                if self.active[k]:
+                    self._g_stage[k].replay() if self.use_graph else self._stage(k)
+                if self.reduced[k]:
+                    works.append(self._reduce_async(k))
             self._t5_ext_join()
             for w in works:
                 w.wait()
-            g[self.S].replay() if self.use_graph else self._opt()
+            self._g_opt.replay() if self.use_graph else self._opt()
         elif self.distributed:
             g[0].replay() if self.use_graph else self._fwd_bwd()
             self._t5_ext_join()

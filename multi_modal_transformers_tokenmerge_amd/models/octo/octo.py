@@ -13,7 +13,10 @@ MI355X design of the step (SURVEY §3.1 call stack):
   head        : diffusion denoise loss (action_heads/diffusion.py)
   optimizer   : one fused AdamW launch over the flat parameter buffer; device step counter;
                 optionally a learning-rate schedule, global-norm clipping and non-finite-step
-                skipping evaluated on the device (AdamW, OCTOTrainState.opt)
+                skipping evaluated on the device (AdamW, OCTOTrainState.opt); optionally
+                parameter groups (a weight-decay mask, frozen parameters: a flag byte per 64
+                elements read by the kernels), and then a backward that stops at the lowest
+                block still trained (Octo.set_param_groups)
 Everything after the input upload is stream-ordered device work with no host sync, so the whole
 step is captured into a HIP graph and replayed (see OCTOTrainState.graphed_step).
 """
@@ -36,7 +39,7 @@ from ...action_heads.diffusion import DiffusionActionHead
 from ...attention_blocks.attention import (LayerCtx, MultiHeadAttentionPooling,
                                            StackedEncoder1DBlock)
 from ...layers import Dense, wgrad_overlap
-from ...params import ParamStore, he_normal, normal
+from ...params import GROUP_CHUNK, ParamStore, he_normal, normal
 from ...schedules import Constant, Schedule, WarmupCosine, WarmupRsqrt
 from ...tokenizers.images.image_tokenizer import ImageTokenizer
 from ...tokenizers.readout.readout import AddPositionEmbedding
@@ -122,6 +125,7 @@ class Octo:
             store.set_deterministic(True)
         self.t5 = T5Tokenizer(cfg.t5).materialize(self.device, seed + 1) if self.has_text else None
         self._merge_sources = None  # the last tracked forward's source buffers (merge_source)
+        self._cut = (0, False)      # where the backward stops (set_param_groups)
         self._build_tables()
 
     # ------------------------------------------------------------------ static tables
@@ -384,6 +388,70 @@ class Octo:
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
+    # ------------------------------------------------------------------ optimizer groups
+    GROUP_PRESETS = {"kernels": ("*/kernel",)}
+
+    def head_prefixes(self) -> List[str]:
+        """Name prefixes of the parameters that belong to an action head, from the head objects
+        (the pooling module is declared under the diffusion head)."""
+        heads = [self.head._name]
+        heads += [h.name for h in (self.continuous_head, self.categorical_head) if h is not None]
+        if self.pooling is not None:
+            heads.append(self.pooling._name)
+        return heads
+
+    def _group_selector(self, value, what: str):
+        """An AdamW group field as ParamStore.set_groups takes it: None, a tuple of patterns (a
+        preset name resolved, a single string one pattern) or, for "head_only", a predicate."""
+        if value is None:
+            return None
+        if isinstance(value, str):
+            if value == "head_only" and what == "frozen_keys":
+                pre = tuple(p + "/" for p in self.head_prefixes())
+                return lambda name: not name.startswith(pre)
+            return self.GROUP_PRESETS.get(value, (value,))
+        if isinstance(value, (list, tuple)) and all(isinstance(v, str) for v in value):
+            return tuple(value)
+        raise ValueError(f"{what}: {value!r} is neither None, a preset / pattern string nor a "
+                         "sequence of pattern strings")
+
+    def set_param_groups(self, weight_decay_mask=None, frozen_keys=None):
+        """Resolve AdamW.weight_decay_mask / frozen_keys against this model's parameter names
+        (ParamStore.set_groups: flags per parameter and the device chunk table; ValueError for a
+        pattern that matches nothing or a request that freezes everything) and place the
+        backward's cut. Both None: no groups, the whole backward."""
+        self.store.set_groups(self._group_selector(weight_decay_mask, "weight_decay_mask"),
+                              self._group_selector(frozen_keys, "frozen_keys"))
+        self._cut = self._backward_cut()
+        return self
+
+    def _backward_cut(self):
+        """(j, tokens_frozen). The store declares the tokenizers, the stem, TextProjection_0,
+        AddPositionEmbedding_0 and posembed_input first, then blocks 0 .. nb-1, then the heads.
+        tokens_frozen: everything declared before block 0 is frozen. j: the lowest block the
+        backward has to reach: the lowest block holding a trainable parameter (nb if none does),
+        or 0 while a parameter before the blocks is trained, whose gradient comes through all of
+        them. The backward runs blocks [j, nb) and the token / stem part only for j == 0 and not
+        tokens_frozen; with j == nb the heads do not produce the sequence gradient at all."""
+        nb = self.cfg.num_blocks
+        off0 = self._block_offset(0)
+        pre = "StackedEncoder1DBlock_0/Block_"
+        tokens_frozen, j = True, nb
+        for p in self.store.params:
+            if p.frozen:
+                continue
+            if p.offset < off0:
+                tokens_frozen = False
+            elif p.name.startswith(pre):
+                j = min(j, int(p.name[len(pre):].split("/", 1)[0]))
+        return (j if tokens_frozen else 0), tokens_frozen
+
+    def stage_active(self, stage: int, stages) -> bool:
+        """Does backward_stage(st, stage, stages) launch anything? Stage 0 always (the heads); a
+        later stage only if it reaches above the cut (with the cut at 0 every stage does; the
+        token / stem backward belongs to the last one)."""
+        return stage == 0 or self.stage_bounds(stages)[stage] > self._cut[0]
+
     # ------------------------------------------------------------------ staged backward
     def _block_offset(self, j: int) -> int:
         """Flat index of block j's first parameter (store.n for j = num_blocks)."""
@@ -446,20 +514,37 @@ class Octo:
 
     def backward_stage(self, st: Dict, stage: int, stages):
         """Stage `stage` of a backward split as stage_bounds(stages) (the heads run in stage 0,
-        the stem / embeddings in the last): backward(st) == all stages in order."""
+        the stem / embeddings in the last): backward(st) == all stages in order.
+        With frozen parameters (set_param_groups) the backward stops at the cut (_backward_cut):
+        a stage that contains it clamps its lower block, a stage wholly below it launches
+        nothing, and the gradients of everything below stay the zeros zero_grad wrote."""
         b = self.stage_bounds(stages)
         n_stages = len(b) - 1
+        cut, tokens_frozen = self._cut
+        if not self.stage_active(stage, b):
+            if stage == n_stages - 1:
+                st.pop("_dx", None)
+                st.pop("_dz", None)
+            return
+        lo, hi = max(b[stage + 1], cut), b[stage]
         with wgrad_overlap(self.device):  # dW products beside the critical path; joined here
             if stage == 0:
                 with phase("bwd/head"):
-                    st["_dx"] = self._backward_head(st)
-            with phase(f"bwd/blocks[{b[stage + 1]},{b[stage]})"):
-                dx = self.stack.backward(st["_dx"], st["stack_sv"], st["ctxs"], lo=b[stage + 1],
-                                         hi=b[stage])
+                    st["_dx"] = self._backward_head(st, need_dx=cut < self.cfg.num_blocks)
+            dx = st["_dx"]
+            if lo < hi:
+                # floor: the stage's lowest block hands the dropout backward of the block below
+                # to the next stage (st["_dz"]), so the stages launch what one backward launches
+                # and give the same bits in deterministic mode
+                with phase(f"bwd/blocks[{lo},{hi})"):
+                    dx, st["_dz"] = self.stack.backward(dx, st["stack_sv"], st["ctxs"], lo=lo,
+                                                        hi=hi, dz=st.pop("_dz", None), floor=cut)
             if stage == n_stages - 1:
-                with phase("bwd/tokens+stem"):
-                    self._backward_tokens(st, dx)
+                if cut == 0 and not tokens_frozen:
+                    with phase("bwd/tokens+stem"):
+                        self._backward_tokens(st, dx)
                 st.pop("_dx", None)
+                st.pop("_dz", None)
             else:
                 st["_dx"] = dx
         if self.store.det_fx is not None:  # deterministic mode: this stage's final region
@@ -468,15 +553,20 @@ class Octo:
     def backward(self, st: Dict):
         """Reverse schedule of compute_diffusion_denoise_loss / compute_l2_loss / compute_ce_loss;
         writes every parameter gradient into the flat gradient buffer (which must be zeroed
-        before the forward)."""
+        before the forward); with frozen parameters, every gradient above the cut
+        (backward_stage)."""
         self.backward_stage(st, 0, 1)
 
-    def _backward_head(self, st: Dict):
+    def _backward_head(self, st: Dict, need_dx: bool = True):
+        """The heads' parameter gradients; returns the gradient of the final sequence, or None
+        with need_dx False (no block is trained: nothing reads it)."""
         B = st["B"]
         D = self.D
         kind = st.get("head_kind", "diffusion")
         if kind == "categorical":
             dg = self.categorical_head.loss_backward(st["head_sv"])
+            if not need_dx:
+                return None
             dxL = torch.empty(st["xL_shape"], dtype=torch.float32, device=dg.device)
             _C.call("mmt_rows_group_mean_bwd", _C.ptr(dg), B, self.L_final, D,
                     _C.ptr(self.readout_group), self.cfg.action_space_dim,
@@ -487,7 +577,12 @@ class Octo:
             if kind == "diffusion" and self.pooling is not None:
                 # readout_flag holds each readout row's slot index: the scatter writes all of dxL
                 with phase("bwd/pool"):
-                    return self.pooling.backward(de, st["pool_sv"], self.readout_flag)
+                    if need_dx:
+                        return self.pooling.backward(de, st["pool_sv"], self.readout_flag)
+                    return self.pooling.backward(de, st["pool_sv"], self.readout_flag,
+                                                 need_dx=False)
+            if not need_dx:
+                return None
             dxL = torch.empty(st["xL_shape"], dtype=torch.float32, device=de.device)
             _C.call("mmt_rows_mean_bwd", _C.ptr(de), de.stride(0), B, self.L_final, D,
                     _C.ptr(self.readout_flag), self.readout_rows.numel(), _C.ptr(dxL),
@@ -525,7 +620,8 @@ class Octo:
 @dataclass
 class AdamW:
     """The reference takes an optax tx from its caller (octo.py:341); this is optax.adamw with
-    these defaults (decoupled weight decay applied to every parameter, as optax without a mask).
+    these defaults (decoupled weight decay applied to every parameter, as optax without a mask,
+    unless weight_decay_mask says otherwise).
 
     learning_rate: a float, or a schedule (schedules.Constant / WarmupCosine / WarmupRsqrt)
     evaluated on the device from the step counter. max_grad_norm: optax.clip_by_global_norm
@@ -533,7 +629,21 @@ class AdamW:
     leaves the parameters and both moments untouched. With a float learning rate and neither
     option the step is the plain mmt_adamw launch; otherwise the learning rate, the gradient norm
     and the clip factor live in device memory (OCTOTrainState.opt), so one captured graph serves
-    the whole schedule."""
+    the whole schedule.
+
+    Parameter groups, optax.multi_transform({"trainable": optax.chain(clip_by_global_norm,
+    adamw(schedule, mask=decay_mask)), "frozen": set_to_zero()}); both default to None, the
+    behaviour above, launch for launch:
+    weight_decay_mask: the parameters that ARE decayed, as fnmatch.fnmatchcase patterns against
+    the full parameter name (one string or a sequence; a name itself is a pattern); the preset
+    "kernels" = ("*/kernel",) is the Octo pre-training recipe (no decay on biases, norm scales,
+    embeddings, fourier_kernel, learnt_q_input).
+    frozen_keys: the parameters that are never updated (same pattern forms): their master, both
+    shadows and both moments keep their bits, they do not enter the gradient norm, and the
+    backward stops below the lowest block it still has to reach (Octo._backward_cut). The preset
+    "head_only" freezes everything outside the action heads.
+    The patterns are resolved in create_octo_train_state, where the model is known: one that
+    matches no parameter, or freezing everything, is a ValueError."""
     learning_rate: Union[float, Constant, WarmupCosine, WarmupRsqrt] = 3e-4
     b1: float = 0.9
     b2: float = 0.999
@@ -541,8 +651,16 @@ class AdamW:
     weight_decay: float = 1e-4
     max_grad_norm: Optional[float] = None
     skip_nonfinite: bool = False
+    weight_decay_mask: Union[None, str, tuple, list] = None
+    frozen_keys: Union[None, str, tuple, list] = None
 
     def __post_init__(self):
+        for what in ("weight_decay_mask", "frozen_keys"):
+            v = getattr(self, what)
+            if not (v is None or isinstance(v, str) or (isinstance(v, (list, tuple))
+                                                        and all(isinstance(x, str) for x in v))):
+                raise ValueError(f"AdamW: {what} {v!r} is neither None, a preset / pattern string "
+                                 "nor a sequence of pattern strings")
         if not isinstance(self.learning_rate, (int, float) + Schedule):
             raise TypeError(f"AdamW: learning_rate {self.learning_rate!r} is neither a number nor "
                             "a schedules.Constant / WarmupCosine / WarmupRsqrt")
@@ -554,6 +672,10 @@ class AdamW:
         """The optimizer's scalars are computed on the device (mmt_optim_prepare)."""
         return (not isinstance(self.learning_rate, (int, float))
                 or self.max_grad_norm is not None or self.skip_nonfinite)
+
+    @property
+    def grouped(self) -> bool:
+        return self.weight_decay_mask is not None or self.frozen_keys is not None
 
     @property
     def schedule(self):
@@ -618,6 +740,12 @@ class OCTOTrainState:
     def step(self) -> int:
         return int(self.rng[1].item())
 
+    @property
+    def param_groups(self) -> Dict[str, Dict[str, bool]]:
+        """name -> {"decay", "frozen"} as the optimizer applies them (AdamW.weight_decay_mask /
+        frozen_keys resolved against the model)."""
+        return self.model.store.param_groups()
+
     def _opt_word(self, i: int) -> float:
         if self.opt is None:
             raise AttributeError("the optimizer keeps no device-side state (plain AdamW: float "
@@ -627,7 +755,8 @@ class OCTOTrainState:
     # host reads of `opt` (each synchronises with the device): the latest step's values
     @property
     def last_grad_norm(self) -> float:
-        """Global norm of the averaged gradient before clipping."""
+        """Global norm of the averaged gradient before clipping, over the trainable parameters
+        (frozen ones do not enter it: optax.multi_transform clips inside the trainable group)."""
         return self._opt_word(_C.OPT_GRAD_NORM)
 
     @property
@@ -650,7 +779,21 @@ class OCTOTrainState:
         s = self.model.store
         tx = self.tx
         grad_scale = getattr(self.allreduce, "grad_scale", 1.0)
-        if self.opt is None:
+        if s.chunk_flags is not None:
+            # parameter groups: the grouped entry points, only when the store holds a flag table
+            n = s.flat.numel()
+            if self.opt is not None:
+                _C.call("mmt_optim_prepare_groups", _C.ptr(s.flat_grad), n, grad_scale,
+                        float(tx.max_grad_norm or 0.0), int(tx.skip_nonfinite),
+                        ctypes.addressof(self._sched_c), _C.ptr(self.rng), _C.ptr(self.opt),
+                        _C.ptr(self.opt_workspace), self.opt_workspace.numel(),
+                        _C.ptr(s.chunk_flags), GROUP_CHUNK, _C.stream_ptr())
+            lr = tx.learning_rate if self.opt is None else 0.0
+            _C.call("mmt_adamw_groups", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
+                    _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt), lr,
+                    tx.b1, tx.b2, tx.eps, tx.weight_decay, grad_scale, _C.ptr(s.chunk_flags),
+                    GROUP_CHUNK, _C.stream_ptr())
+        elif self.opt is None:
             _C.call("mmt_adamw", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m), _C.ptr(s.v),
                     _C.ptr(s.flat_bf16), s.flat.numel(), _C.ptr(self.rng), tx.learning_rate, tx.b1,
                     tx.b2, tx.eps, tx.weight_decay, grad_scale, _C.stream_ptr())
@@ -674,15 +817,23 @@ class OCTOTrainState:
 
 def create_octo_train_state(model: Octo, tx: AdamW | None = None, seed: int = 1234,
                             allreduce=None, sample_offset: int = 0) -> OCTOTrainState:
-    """Reference octo.py:334-386 (parameters were initialised by Octo(...))."""
+    """Reference octo.py:334-386 (parameters were initialised by Octo(...)). The optimizer's
+    parameter groups are resolved here (Octo.set_param_groups: ValueError for a pattern that
+    matches no parameter or a request that freezes everything); they live on the model's store,
+    so the latest state created for a model decides them."""
+    tx = tx or AdamW()
+    model.set_param_groups(tx.weight_decay_mask, tx.frozen_keys)
     rng = torch.tensor([seed, 0], dtype=torch.int32, device=model.device)
-    return OCTOTrainState(model, tx or AdamW(), rng, allreduce, sample_offset,
+    return OCTOTrainState(model, tx, rng, allreduce, sample_offset,
                           metrics=OCTOMetrics(model.device))
 
 
 def grads_tree(model: Octo) -> Dict[str, torch.Tensor]:
     """The step's gradients by parameter name (views into the flat fp32 gradient buffer, valid
-    until the next step zeroes it) — the ``grads`` the reference's train steps return."""
+    until the next step zeroes it) — the ``grads`` the reference's train steps return. With frozen
+    parameters (AdamW.frozen_keys) the backward stops at the cut (Octo._backward_cut): gradients
+    below it are exactly zero, zero_grad's value; a frozen parameter above the cut still shows its
+    gradient, which the optimizer ignores."""
     return {p.name: p.grad for p in model.store.params}
 
 

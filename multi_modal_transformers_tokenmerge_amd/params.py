@@ -10,7 +10,9 @@ into, zeroed by one memset per step) and the AdamW moments. Consequences on MI35
 Views are 64-element aligned (256 B) so every GEMM operand base is 16-B aligned.
 
 Frozen parameters (the T5 encoder, t5_base.py:14 stop_gradient) live in a separate bf16-only
-store: they have no master copy, no gradient and no optimizer state.
+store: they have no master copy, no gradient and no optimizer state. A parameter of this store
+frozen by the optimizer (AdamW.frozen_keys, ParamStore.set_groups) keeps all its buffers; the
+optimizer kernels skip its 64-element chunks.
 
 Initialisers restate the Flax ones the reference's YAML names (he_normal = variance_scaling(2,
 fan_in, truncated_normal), normal(0.01) biases, LayerNorm ones/zeros, ...).
@@ -25,6 +27,9 @@ from typing import Callable, Dict, List, Tuple
 import torch
 
 ALIGN = 64
+# optimizer groups (include/mmt_api.h MMT_GROUP_*): one flag byte per GROUP_CHUNK elements
+GROUP_CHUNK, GROUP_NO_DECAY, GROUP_FROZEN = 64, 1, 2
+assert ALIGN % GROUP_CHUNK == 0  # a chunk never straddles two parameters
 
 
 def _fans(shape, in_axis=-2, out_axis=-1):
@@ -85,6 +90,8 @@ class Param:
     q8: torch.Tensor | None = None        # (rows, cols) uint8 e4m3 view
     q8_scale: torch.Tensor | None = None  # (rows,) fp32
     grad: torch.Tensor | None = None      # fp32 grad view
+    decay: bool = True                    # optimizer groups (ParamStore.set_groups): weight decay
+    frozen: bool = False                  # applies / the parameter is never updated
 
     @property
     def numel(self):
@@ -190,6 +197,65 @@ class ParamStore:
 
     def zero_grad(self):
         self.flat_grad.zero_()
+
+    # ------------------------------------------------------------------ optimizer groups
+    # chunk_flags: None (every parameter decayed and trained: the plain optimizer launches), or
+    # one uint8 per GROUP_CHUNK elements of the flat buffers on their device (include/mmt_api.h
+    # mmt_adamw_groups). Offsets are ALIGN-aligned, so a chunk never straddles two parameters; a
+    # parameter's padding chunks carry its flags.
+    chunk_flags = None
+
+    def set_groups(self, decay=None, frozen=None):
+        """The optimizer groups of optax.multi_transform({"trainable": adamw(mask=decay),
+        "frozen": set_to_zero()}). `decay` selects the parameters that take weight decay (None:
+        all), `frozen` those that are never updated (None: none); each is a sequence of
+        fnmatch.fnmatchcase patterns matched against the full parameter name, or a predicate
+        name -> bool. Both None drops the groups (chunk_flags None). A pattern that matches no
+        parameter and a request that freezes every parameter raise ValueError. Sets
+        Param.decay / Param.frozen and uploads the chunk table; call after materialize()."""
+        if self.flat is None:
+            raise RuntimeError("set_groups: materialize() the store first")
+        dec = self._select(decay, "weight_decay_mask", True)
+        frz = self._select(frozen, "frozen_keys", False)
+        if self.params and all(frz):
+            raise ValueError("frozen_keys freeze every parameter: nothing is left to train")
+        for p, d, f in zip(self.params, dec, frz):
+            p.decay, p.frozen = d, f
+        if decay is None and frozen is None:
+            self.chunk_flags = None
+            return self
+        table = torch.zeros((self.n + GROUP_CHUNK - 1) // GROUP_CHUNK, dtype=torch.uint8)
+        for i, p in enumerate(self.params):  # up to the next parameter: the padding included
+            end = self.params[i + 1].offset if i + 1 < len(self.params) else self.n
+            table[p.offset // GROUP_CHUNK:(end + GROUP_CHUNK - 1) // GROUP_CHUNK] = (
+                (0 if p.decay else GROUP_NO_DECAY) | (GROUP_FROZEN if p.frozen else 0))
+        self.chunk_flags = table.to(self.flat.device)
+        return self
+
+    def _select(self, sel, what: str, default: bool) -> List[bool]:
+        if sel is None:
+            return [default] * len(self.params)
+        if callable(sel):
+            return [bool(sel(p.name)) for p in self.params]
+        import fnmatch
+        pats = list(sel)
+        hit = [[fnmatch.fnmatchcase(p.name, pat) for pat in pats] for p in self.params]
+        for j, pat in enumerate(pats):
+            if not any(h[j] for h in hit):
+                raise ValueError(f"{what}: pattern {pat!r} matches no parameter")
+        return [any(h) for h in hit]
+
+    @property
+    def trainable_numel(self) -> int:
+        """Elements of the parameters that are not frozen (padding not counted)."""
+        return sum(p.numel for p in self.params if not p.frozen)
+
+    def param_groups(self) -> Dict[str, Dict[str, bool]]:
+        return {p.name: {"decay": p.decay, "frozen": p.frozen} for p in self.params}
+
+    def region_trainable(self, lo: int, hi: int) -> bool:
+        """Does the flat range [lo, hi) hold an element of a parameter that is trained?"""
+        return any(not p.frozen and p.offset < hi and p.offset + p.numel > lo for p in self.params)
 
     # ------------------------------------------------------------------ deterministic mode
     det_fx = None  # int64 fixed-point shadow of flat_grad while the mode is on

@@ -4,15 +4,18 @@
     python tools/optim_probe.py --step --batch 512 # + the graphed single-GPU train step
 
 * kernels: mmt_adamw (the yardstick), mmt_adamw_dev and mmt_optim_prepare (both of its launches)
-  over the flat parameter count of octo_small and ref_octo_base. HIP events around batches of
-  --inner launches, the three variants interleaved (in rotating order) over --rounds rounds in
-  one process after a warm-up of every variant; per launch: median, min and the 10th..90th
-  percentile spread. The buffers (18 B of state + 4 B of gradient per parameter, 0.4 GB at
+  over the flat parameter count of octo_small and ref_octo_base, and the grouped launches
+  mmt_adamw_groups / mmt_optim_prepare_groups with three chunk-flag tables of that model: no bit
+  set ("none"), AdamW(weight_decay_mask="kernels") and AdamW(frozen_keys="head_only"). HIP
+  events around batches of --inner launches, all variants interleaved (in rotating order) over
+  --rounds rounds in one process after a warm-up of every variant; per launch: median, min and
+  the 10th..90th percentile spread. The buffers (18 B of state + 4 B of gradient per parameter, 0.4 GB at
   22.5 M) exceed the 256 MB Infinity Cache, so the launches stream from HBM as in a training
   step.
 * --step: ms per step of distributed.DDPStep's one-graph step at the bench configuration with
-  the default AdamW() and with a warm-up-cosine schedule + clipping + skip_nonfinite, the two
-  step objects alternating in blocks of --step-block steps.
+  the default AdamW(), with a warm-up-cosine schedule + clipping + skip_nonfinite, and with
+  AdamW(frozen_keys="head_only") (the backward stops at the heads), the step objects alternating
+  in blocks of --step-block steps.
 
 Prints one JSON line. Needs a GPU: there is no fallback.
 """
@@ -39,9 +42,19 @@ HYPER = (0.9, 0.999, 1e-8, 1e-4)
 HBM_PEAK_GBS = 8000.0  # MI355X (MI355X_MICROARCH.md, chip table)
 
 
-def flat_count(config: str) -> int:
-    """Elements of the flat fp32 master buffer (what AdamW runs over), counted on the CPU."""
-    return O.Octo(get_config(config), torch.device("cpu"), seed=0).store.flat.numel()
+GROUP_TABLES = {"none": dict(weight_decay_mask="*"), "kernels": dict(weight_decay_mask="kernels"),
+                "head_only": dict(frozen_keys="head_only")}
+
+
+def flat_count(config: str):
+    """Elements of the flat fp32 master buffer (what AdamW runs over) and the chunk-flag tables
+    of GROUP_TABLES for that model, from a model built on the CPU."""
+    model = O.Octo(get_config(config), torch.device("cpu"), seed=0)
+    tables = {}
+    for name, kw in GROUP_TABLES.items():
+        model.set_param_groups(kw.get("weight_decay_mask"), kw.get("frozen_keys"))
+        tables[name] = model.store.chunk_flags.clone()
+    return model.store.flat.numel(), tables
 
 
 def _stats(us):
@@ -51,7 +64,7 @@ def _stats(us):
                 p90_us=round(float(np.percentile(a, 90)), 2))
 
 
-def probe_kernels(n: int, dev, rounds: int, inner: int, warm: int) -> dict:
+def probe_kernels(n: int, tables: dict, dev, rounds: int, inner: int, warm: int) -> dict:
     gen = torch.Generator(device=dev).manual_seed(0)
     p = torch.randn(n, generator=gen, device=dev)
     g = torch.randn(n, generator=gen, device=dev) * 1e-2
@@ -76,6 +89,22 @@ def probe_kernels(n: int, dev, rounds: int, inner: int, warm: int) -> dict:
                 _C.ptr(state), _C.ptr(opt), _C.ptr(ws), ws.numel(), s)
 
     variants = {"mmt_adamw": adamw, "mmt_adamw_dev": adamw_dev, "mmt_optim_prepare": prepare}
+    flags = {k: t.to(dev) for k, t in tables.items()}
+    assert all(t.numel() == -(-n // 64) for t in flags.values())
+
+    def adamw_groups(t):
+        return lambda: _C.call("mmt_adamw_groups", _C.ptr(p), _C.ptr(g), _C.ptr(m), _C.ptr(v),
+                               _C.ptr(shadow), n, _C.ptr(state), None, 3e-4, *HYPER, 1.0,
+                               _C.ptr(t), 64, s)
+
+    def prepare_groups(t):
+        return lambda: _C.call("mmt_optim_prepare_groups", _C.ptr(g), n, 1.0, 1.0, 1,
+                               ctypes.addressof(sched), _C.ptr(state), _C.ptr(opt), _C.ptr(ws),
+                               ws.numel(), _C.ptr(t), 64, s)
+
+    for k, t in flags.items():
+        variants[f"mmt_adamw_groups[{k}]"] = adamw_groups(t)
+        variants[f"mmt_optim_prepare_groups[{k}]"] = prepare_groups(t)
     prepare()  # opt holds a learning rate and a clip factor before the first mmt_adamw_dev
     for fn in variants.values():
         for _ in range(warm):
@@ -84,7 +113,8 @@ def probe_kernels(n: int, dev, rounds: int, inner: int, warm: int) -> dict:
     times = {k: [] for k in variants}
     names = list(variants)
     for r in range(rounds):
-        for name in names[r % 3:] + names[:r % 3]:  # every variant follows every other one
+        k = r % len(names)
+        for name in names[k:] + names[:k]:  # every variant follows every other one
             fn = variants[name]
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -103,6 +133,15 @@ def probe_kernels(n: int, dev, rounds: int, inner: int, warm: int) -> dict:
     gbs = 4.0 * n / out["mmt_optim_prepare"]["median_us"] / 1e3      # 4 B per parameter
     out["prepare_gbs"] = round(gbs, 1)
     out["prepare_hbm_fraction"] = round(gbs / HBM_PEAK_GBS, 3)
+    prep = out["mmt_optim_prepare"]
+    for k in flags:  # the grouped launches against the plain kernel of the same build
+        a, q = out[f"mmt_adamw_groups[{k}]"], out[f"mmt_optim_prepare_groups[{k}]"]
+        out[f"adamw_groups[{k}]_over_adamw"] = round(a["median_us"] / base["median_us"], 4)
+        out[f"prepare_groups[{k}]_over_prepare"] = round(q["median_us"] / prep["median_us"], 4)
+    a = out["mmt_adamw_groups[none]"]["median_us"]
+    out["adamw_groups[none]_inside_adamw_p10_p90"] = bool(base["p10_us"] <= a <= base["p90_us"])
+    q = out["mmt_optim_prepare_groups[none]"]["median_us"]
+    out["prepare_groups[none]_inside_prepare_p10_p90"] = bool(prep["p10_us"] <= q <= prep["p90_us"])
     return out
 
 
@@ -114,7 +153,8 @@ def probe_step(config: str, B: int, dev, steps: int, block: int, warm: int) -> d
     runs = {}
     for name, tx in (("default", O.AdamW()),
                      ("schedule_clip", O.AdamW(WarmupCosine(0.0, 3e-4, 2000, 300000, 3e-5),
-                                               max_grad_norm=1.0, skip_nonfinite=True))):
+                                               max_grad_norm=1.0, skip_nonfinite=True)),
+                     ("head_only", O.AdamW(frozen_keys="head_only"))):
         model = O.Octo(get_config(config), dev, seed=0)
         cfg, H = model.cfg, model.cfg.image_size[0]
         if not runs:
@@ -150,6 +190,8 @@ def probe_step(config: str, B: int, dev, steps: int, block: int, warm: int) -> d
             out[name].update(last_lr=state.last_lr, last_grad_norm=state.last_grad_norm,
                              last_clip=state.last_clip, skipped_steps=state.skipped_steps)
     out["delta_us"] = round((out["schedule_clip"]["median_ms"] - out["default"]["median_ms"]) * 1e3, 1)
+    out["head_only_over_default"] = round(out["head_only"]["median_ms"]
+                                          / out["default"]["median_ms"], 4)
     return out
 
 
@@ -172,8 +214,9 @@ def main():
     res = {"device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "inner": args.inner,
            "kernels": {}}
     for c in args.configs:
-        n = flat_count(c)
-        res["kernels"][c] = dict(n=n, **probe_kernels(n, dev, args.rounds, args.inner, args.warmup))
+        n, tables = flat_count(c)
+        res["kernels"][c] = dict(n=n, **probe_kernels(n, tables, dev, args.rounds, args.inner,
+                                                      args.warmup))
     if args.step:
         res["step"] = dict(config=args.step_config, batch=args.batch, steps=args.steps,
                            **probe_step(args.step_config, args.batch, dev, args.steps,
