@@ -843,6 +843,56 @@ int mmt_optim_prepare_groups(const float* g, int64_t n, float grad_scale, double
                              int64_t ws_bytes, const uint8_t* chunk_flags, int chunk,
                              mmt_stream_t stream);
 
+/* Parameter EMA: the exponential moving average of the weights that diffusion recipes evaluate
+ * (DDPM, Diffusion Policy, diffusers EMAModel; optax.ema(decay, debias = False) over the
+ * parameters), kept in a second flat fp32 buffer `ema` of n elements and updated inside the AdamW
+ * launch, where the new parameter is in a register:
+ *   ema[i] = d_f * ema[i] + omd_f * p_new[i]
+ * (one product, one fused multiply-add: two fp32 roundings).
+ *
+ * Decay of s = state[1] (the count BEFORE this step's advance, as the schedules above):
+ *   MMT_EMA_CONSTANT  d = value
+ *   MMT_EMA_WARMUP    the diffusers / Diffusion-Policy EMAModel rule:
+ *                     k = max(0, s - update_after_step - 1); d = 0 if k == 0, else
+ *                     min(max_value, max(min_value, 1 - (1 + k / inv_gamma)^(-power)))
+ * d and 1 - d are formed in double on the device and each rounded once to fp32 (d_f, omd_f), as
+ * the betas are: one captured graph serves the whole warm-up. d = 0 makes ema a copy of p_new.
+ *
+ * mmt_adamw_ema covers the three AdamW forms and takes every argument of theirs:
+ *   opt == NULL, chunk_flags == NULL   mmt_adamw (lr, grad_scale from the host arguments)
+ *   opt != NULL, chunk_flags == NULL   mmt_adamw_dev (lr, grad_scale ignored)
+ *   chunk_flags != NULL                mmt_adamw_groups (either opt form; chunk must be
+ *                                      MMT_GROUP_CHUNK)
+ * It has the launch geometry of the kernel it replaces and calls the same per-element update
+ * function, so p, m, v and the shadow are bit-identical to that kernel's on the same inputs. A
+ * FROZEN chunk issues no load or store of ema either (a caller that initialises ema as a copy of
+ * p keeps ema == p there). opt[6] != 0 (a skipped step) returns at once: ema is not touched, so
+ * a skipped step does not enter the average, though it advances s. The opt words are only read.
+ *
+ * mmt_ema_swap exchanges p[i] and ema[i] and writes shadow[i] = bf16(new p[i]) in one pass
+ * (shadow_bf16 may be NULL), for evaluating with the averaged weights in place: no buffer moves,
+ * so captured graphs stay valid. chunk_flags may be NULL; FROZEN chunks are not touched. Applied
+ * twice it is the identity, bit for bit.
+ *
+ * MMT_ERR_INVALID before any launch: a null p, g, m, v, state, ema or decay; n <= 0; chunk_flags
+ * given with chunk != MMT_GROUP_CHUNK; an unknown kind; value, max_value or min_value outside
+ * [0, 1]; for MMT_EMA_WARMUP also min_value > max_value, inv_gamma <= 0, power < 0,
+ * update_after_step < 0. */
+enum { MMT_EMA_CONSTANT = 0, MMT_EMA_WARMUP = 1 };
+typedef struct {            /* zero-initialise, then set; read on the host at launch */
+  int kind;
+  double value;                               /* CONSTANT only */
+  double max_value, min_value;                /* WARMUP only, as the fields below */
+  double inv_gamma, power;
+  int64_t update_after_step;
+} mmt_ema_decay_t;
+int mmt_adamw_ema(float* p, const float* g, float* m, float* v, void* shadow_bf16, float* ema,
+                  int64_t n, const int32_t* state, const float* opt, double lr, double b1,
+                  double b2, double eps, double wd, float grad_scale, const uint8_t* chunk_flags,
+                  int chunk, const mmt_ema_decay_t* decay, mmt_stream_t stream);
+int mmt_ema_swap(float* p, float* ema, void* shadow_bf16, int64_t n, const uint8_t* chunk_flags,
+                 int chunk, mmt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,8 @@ SIGNATURES: dict[str, list] = {
     "mmt_adamw_dev": [P, P, P, P, P, L, P, P, D, D, D, D, P],
     "mmt_adamw_groups": [P, P, P, P, P, L, P, P, D, D, D, D, D, F, P, I, P],
     "mmt_optim_prepare_groups": [P, L, F, D, I, P, P, P, P, L, P, I, P],
+    "mmt_adamw_ema": [P, P, P, P, P, P, L, P, P, D, D, D, D, D, F, P, I, P, P],
+    "mmt_ema_swap": [P, P, P, L, P, I, P],
 }
 _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)

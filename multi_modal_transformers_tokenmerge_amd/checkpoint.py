@@ -456,6 +456,8 @@ def save_train_state(path: str, train_state) -> None:
         # device-side optimizer words (the skipped-step count; the rest is rewritten every
         # step). The schedule itself needs nothing saved: it is a function of rng[1].
         d["opt"] = train_state.opt.cpu()
+    if s.ema is not None:  # the parameter EMA (AdamW.ema_decay)
+        d["ema"] = s.ema.cpu()
     torch.save(d, path)
 
 
@@ -474,4 +476,8 @@ def load_train_state(path: str, train_state) -> None:
             train_state.opt.copy_(d["opt"].to(train_state.opt.device))
         else:  # a file written before the optimizer kept device-side words
             train_state.opt.zero_()
+    if s.ema is not None:
+        # a file without an EMA (written by a run that kept none) starts the average at the
+        # loaded master; a file's EMA is ignored by a state that keeps none
+        s.ema.copy_(d["ema"].to(s.ema.device) if "ema" in d else s.flat)
     s.sync_shadow()

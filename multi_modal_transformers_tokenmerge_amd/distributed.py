@@ -273,6 +273,8 @@ class DDPStep:
             snap += [s.metrics.total.clone(), s.metrics.count.clone()]
         if s.opt is not None:  # device-side optimizer words (the skipped-step count accumulates)
             snap.append(s.opt.clone())
+        if st.ema is not None:  # the parameter EMA (AdamW.ema_decay): the warm-up steps move it
+            snap.append(st.ema.clone())
         return snap
 
     def _restore(self, snap):
@@ -282,6 +284,8 @@ class DDPStep:
             dst += [s.metrics.total, s.metrics.count]
         if s.opt is not None:
             dst.append(s.opt)
+        if st.ema is not None:
+            dst.append(st.ema)
         for d, v in zip(dst, snap):
             d.copy_(v)
         st.refresh_transposed()
@@ -295,7 +299,9 @@ class DDPStep:
         shadows are re-derived from the restored bf16 shadow; tests/test_train_state_gpu.py
         checks every buffer bitwise). The snapshot holds one extra copy of the fp32 master, the
         bf16 shadow and both AdamW moments during build(): 14 bytes per parameter (≈ 315 MB for
-        OCTO-small's 22.5 M, ≈ 1.2 GB for OCTO-base), freed before capture."""
+        OCTO-small's 22.5 M, ≈ 1.2 GB for OCTO-base), freed before capture. With a parameter EMA
+        (AdamW.ema_decay) its fp32 buffer is snapshotted too: 18 bytes per parameter (≈ 405 MB
+        and ≈ 1.5 GB)."""
         self._t5_prime()
         if not self.use_graph:
             return self

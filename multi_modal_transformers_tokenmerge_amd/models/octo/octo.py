@@ -16,7 +16,8 @@ MI355X design of the step (SURVEY §3.1 call stack):
                 skipping evaluated on the device (AdamW, OCTOTrainState.opt); optionally
                 parameter groups (a weight-decay mask, frozen parameters: a flag byte per 64
                 elements read by the kernels), and then a backward that stops at the lowest
-                block still trained (Octo.set_param_groups)
+                block still trained (Octo.set_param_groups); optionally an EMA of the
+                parameters updated in the same launch (AdamW.ema_decay, ema_weights())
 Everything after the input upload is stream-ordered device work with no host sync, so the whole
 step is captured into a HIP graph and replayed (see OCTOTrainState.graphed_step).
 """
@@ -40,7 +41,8 @@ from ...attention_blocks.attention import (LayerCtx, MultiHeadAttentionPooling,
                                            StackedEncoder1DBlock)
 from ...layers import Dense, wgrad_overlap
 from ...params import GROUP_CHUNK, ParamStore, he_normal, normal
-from ...schedules import Constant, Schedule, WarmupCosine, WarmupRsqrt
+from ...schedules import (Constant, ConstantEmaDecay, EmaDecay, Schedule, WarmupCosine,
+                          WarmupRsqrt)
 from ...tokenizers.images.image_tokenizer import ImageTokenizer
 from ...tokenizers.readout.readout import AddPositionEmbedding
 from ...tokenizers.text.t5_base import T5Tokenizer
@@ -643,7 +645,16 @@ class AdamW:
     backward stops below the lowest block it still has to reach (Octo._backward_cut). The preset
     "head_only" freezes everything outside the action heads.
     The patterns are resolved in create_octo_train_state, where the model is known: one that
-    matches no parameter, or freezing everything, is a ValueError."""
+    matches no parameter, or freezing everything, is a ValueError.
+
+    ema_decay: keep an exponential moving average of the parameters (ParamStore.ema), updated
+    inside the AdamW launch (mmt_adamw_ema in place of whichever launch the options above select;
+    the parameters, moments and shadows keep their bits). None (the default): off, the launches
+    above. A float in [0, 1): a constant decay (optax.ema(decay, debias=False) over the
+    parameters). A schedules.EmaDecay: the diffusers / Diffusion-Policy EMAModel warm-up, evaluated
+    on the device from the step counter. A skipped step (skip_nonfinite) leaves the average as it
+    is; frozen parameters' average stays equal to them. OCTOTrainState.ema_weights() evaluates
+    with it."""
     learning_rate: Union[float, Constant, WarmupCosine, WarmupRsqrt] = 3e-4
     b1: float = 0.9
     b2: float = 0.999
@@ -653,8 +664,15 @@ class AdamW:
     skip_nonfinite: bool = False
     weight_decay_mask: Union[None, str, tuple, list] = None
     frozen_keys: Union[None, str, tuple, list] = None
+    ema_decay: Union[None, float, EmaDecay] = None
 
     def __post_init__(self):
+        d = self.ema_decay
+        if isinstance(d, bool) or not (d is None or isinstance(d, (int, float, EmaDecay))):
+            raise TypeError(f"AdamW: ema_decay {d!r} is neither None, a float in [0, 1) nor a "
+                            "schedules.EmaDecay")
+        if isinstance(d, (int, float)) and not 0.0 <= d < 1.0:
+            raise ValueError(f"AdamW: ema_decay {d} outside [0, 1)")
         for what in ("weight_decay_mask", "frozen_keys"):
             v = getattr(self, what)
             if not (v is None or isinstance(v, str) or (isinstance(v, (list, tuple))
@@ -681,6 +699,12 @@ class AdamW:
     def schedule(self):
         lr = self.learning_rate
         return Constant(float(lr)) if isinstance(lr, (int, float)) else lr
+
+    @property
+    def ema_schedule(self):
+        """None, or the decay as a schedules.ConstantEmaDecay / EmaDecay."""
+        d = self.ema_decay
+        return ConstantEmaDecay(float(d)) if isinstance(d, (int, float)) else d
 
 
 class OCTOMetrics:
@@ -731,10 +755,66 @@ class OCTOTrainState:
             self.opt_workspace = torch.empty(_C.workspace_size(_C.WS_GRAD_NORM, n),
                                              dtype=torch.uint8, device=dev)
         self._sched_c = self.tx.schedule.to_c() if self.tx.device_control else None
+        # parameter EMA (tx.ema_decay): the mmt_ema_decay_t the AdamW launch reads; the buffer
+        # lives on the store (ParamStore.ema), so the latest state of a model decides it
+        self._ema_c = self.tx.ema_schedule.to_c() if self.tx.ema_decay is not None else None
+        self._ema_swapped = False  # inside ema_weights(): the master holds the EMA
 
     @property
     def params(self):
         return self.model.store.state_dict()
+
+    def _ema_buffer(self) -> torch.Tensor:
+        ema = self.model.store.ema if self._ema_c is not None else None
+        if ema is None:
+            raise AttributeError("the train state keeps no parameter EMA (AdamW.ema_decay is None, "
+                                 "or a later state of this model dropped it)")
+        return ema
+
+    @property
+    def ema_params(self) -> Dict[str, torch.Tensor]:
+        """name -> fp32 view into the EMA buffer (the averaged weights; inside ema_weights() the
+        buffer holds the raw iterate instead)."""
+        self._ema_buffer()
+        return self.model.store.ema_state_dict()
+
+    @property
+    def last_ema_decay(self) -> float:
+        """The decay the latest step applied: the host restatement (schedules.EmaDecay.__call__)
+        at the count before that step's advance. A host read of the step counter."""
+        self._ema_buffer()
+        return self.tx.ema_schedule(max(self.step - 1, 0))
+
+    def ema_weights(self):
+        """``with state.ema_weights(): ...`` evaluates with the averaged weights: mmt_ema_swap
+        exchanges the master and the EMA in place and rewrites the bf16 shadow, then the
+        transposed and e4m3 shadows are re-derived; the same again on exit. No buffer moves, so
+        captured graphs stay valid, and every reader of the store (predict_diffusion_action, the
+        losses with train=False, to_flax_params) sees the EMA inside the block. Frozen chunks
+        are not touched (their EMA equals them). apply_gradients inside the block and a nested
+        entry raise RuntimeError; a state without EMA raises AttributeError."""
+        import contextlib
+        self._ema_buffer()
+
+        @contextlib.contextmanager
+        def _cm():
+            if self._ema_swapped:
+                raise RuntimeError("ema_weights(): already inside the block")
+            self._ema_swap()
+            self._ema_swapped = True
+            try:
+                yield self
+            finally:
+                self._ema_swapped = False
+                self._ema_swap()
+        return _cm()
+
+    def _ema_swap(self):
+        s = self.model.store
+        _C.call("mmt_ema_swap", _C.ptr(s.flat), _C.ptr(self._ema_buffer()), _C.ptr(s.flat_bf16),
+                s.flat.numel(), _C.ptr(s.chunk_flags), GROUP_CHUNK, _C.stream_ptr())
+        s.refresh_transposed()
+        s.refresh_fp8()
 
     @property
     def step(self) -> int:
@@ -776,9 +856,14 @@ class OCTOTrainState:
             self._apply_gradients()
 
     def _apply_gradients(self):
+        if self._ema_swapped:
+            raise RuntimeError("apply_gradients inside ema_weights(): the master buffer holds "
+                               "the EMA, not the iterate")
         s = self.model.store
         tx = self.tx
         grad_scale = getattr(self.allreduce, "grad_scale", 1.0)
+        # parameter EMA: mmt_adamw_ema takes the place of whichever AdamW launch is chosen below
+        ema = s.ema if self._ema_c is not None else None
         if s.chunk_flags is not None:
             # parameter groups: the grouped entry points, only when the store holds a flag table
             n = s.flat.numel()
@@ -789,14 +874,17 @@ class OCTOTrainState:
                         _C.ptr(self.opt_workspace), self.opt_workspace.numel(),
                         _C.ptr(s.chunk_flags), GROUP_CHUNK, _C.stream_ptr())
             lr = tx.learning_rate if self.opt is None else 0.0
-            _C.call("mmt_adamw_groups", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
-                    _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt), lr,
-                    tx.b1, tx.b2, tx.eps, tx.weight_decay, grad_scale, _C.ptr(s.chunk_flags),
-                    GROUP_CHUNK, _C.stream_ptr())
+            if ema is None:
+                _C.call("mmt_adamw_groups", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
+                        _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt),
+                        lr, tx.b1, tx.b2, tx.eps, tx.weight_decay, grad_scale,
+                        _C.ptr(s.chunk_flags), GROUP_CHUNK, _C.stream_ptr())
         elif self.opt is None:
-            _C.call("mmt_adamw", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m), _C.ptr(s.v),
-                    _C.ptr(s.flat_bf16), s.flat.numel(), _C.ptr(self.rng), tx.learning_rate, tx.b1,
-                    tx.b2, tx.eps, tx.weight_decay, grad_scale, _C.stream_ptr())
+            if ema is None:
+                _C.call("mmt_adamw", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
+                        _C.ptr(s.v), _C.ptr(s.flat_bf16), s.flat.numel(), _C.ptr(self.rng),
+                        tx.learning_rate, tx.b1, tx.b2, tx.eps, tx.weight_decay, grad_scale,
+                        _C.stream_ptr())
         else:
             # after the all-reduce, so every rank reduces the same summed gradient to the same
             # bits. A skipped step (skip_nonfinite) still refreshes the shadows (a no-op on
@@ -807,9 +895,17 @@ class OCTOTrainState:
                     float(tx.max_grad_norm or 0.0), int(tx.skip_nonfinite),
                     ctypes.addressof(self._sched_c), _C.ptr(self.rng), _C.ptr(self.opt),
                     _C.ptr(self.opt_workspace), self.opt_workspace.numel(), _C.stream_ptr())
-            _C.call("mmt_adamw_dev", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
-                    _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt),
-                    tx.b1, tx.b2, tx.eps, tx.weight_decay, _C.stream_ptr())
+            if ema is None:
+                _C.call("mmt_adamw_dev", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m),
+                        _C.ptr(s.v), _C.ptr(s.flat_bf16), n, _C.ptr(self.rng), _C.ptr(self.opt),
+                        tx.b1, tx.b2, tx.eps, tx.weight_decay, _C.stream_ptr())
+        if ema is not None:
+            lr = tx.learning_rate if self.opt is None else 0.0
+            _C.call("mmt_adamw_ema", _C.ptr(s.flat), _C.ptr(s.flat_grad), _C.ptr(s.m), _C.ptr(s.v),
+                    _C.ptr(s.flat_bf16), _C.ptr(ema), s.flat.numel(), _C.ptr(self.rng),
+                    _C.ptr(self.opt), lr, tx.b1, tx.b2, tx.eps, tx.weight_decay, grad_scale,
+                    _C.ptr(s.chunk_flags), GROUP_CHUNK, ctypes.addressof(self._ema_c),
+                    _C.stream_ptr())
         s.refresh_transposed()
         s.refresh_fp8()
         _C.call("mmt_step_advance", _C.ptr(self.rng), _C.stream_ptr())
@@ -820,9 +916,11 @@ def create_octo_train_state(model: Octo, tx: AdamW | None = None, seed: int = 12
     """Reference octo.py:334-386 (parameters were initialised by Octo(...)). The optimizer's
     parameter groups are resolved here (Octo.set_param_groups: ValueError for a pattern that
     matches no parameter or a request that freezes everything); they live on the model's store,
-    so the latest state created for a model decides them."""
+    so the latest state created for a model decides them. The same holds for the parameter EMA
+    (AdamW.ema_decay): allocated here as a copy of the master, dropped when tx has none."""
     tx = tx or AdamW()
     model.set_param_groups(tx.weight_decay_mask, tx.frozen_keys)
+    model.store.set_ema(tx.ema_decay is not None)  # a copy of the master, or dropped
     rng = torch.tensor([seed, 0], dtype=torch.int32, device=model.device)
     return OCTOTrainState(model, tx, rng, allreduce, sample_offset,
                           metrics=OCTOMetrics(model.device))

@@ -8,6 +8,8 @@ into, zeroed by one memset per step) and the AdamW moments. Consequences on MI35
     xGMI) instead of hundreds of small tensors;
   * no per-parameter allocation or autograd accumulation kernels exist on the hot path.
 Views are 64-element aligned (256 B) so every GEMM operand base is 16-B aligned.
+A further, optional flat buffer holds an exponential moving average of the master (ParamStore.ema,
+AdamW.ema_decay), updated by the same optimizer launch (mmt_adamw_ema).
 
 Frozen parameters (the T5 encoder, t5_base.py:14 stop_gradient) live in a separate bf16-only
 store: they have no master copy, no gradient and no optimizer state. A parameter of this store
@@ -104,6 +106,7 @@ class ParamStore:
         self.by_name: Dict[str, Param] = {}
         self.n = 0
         self.flat = self.flat_bf16 = self.flat_grad = self.m = self.v = None
+        self.ema = None  # flat fp32 EMA of the master (set_ema; AdamW.ema_decay), or None
 
     def add(self, name: str, shape, init, transposed: bool = False, fp8: bool = False) -> Param:
         if name in self.by_name:
@@ -197,6 +200,18 @@ class ParamStore:
 
     def zero_grad(self):
         self.flat_grad.zero_()
+
+    def set_ema(self, on: bool):
+        """Allocate the parameter EMA as a copy of the master (n fp32 elements, updated by
+        mmt_adamw_ema), or drop it. A frozen chunk's EMA is never written: it stays the copy."""
+        self.ema = self.flat.clone() if on else None
+        return self
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """name -> fp32 view into the EMA buffer."""
+        if self.ema is None:
+            raise AttributeError("the store keeps no parameter EMA (AdamW.ema_decay is None)")
+        return {p.name: self.ema[p.offset:p.offset + p.numel].view(p.shape) for p in self.params}
 
     # ------------------------------------------------------------------ optimizer groups
     # chunk_flags: None (every parameter decayed and trained: the plain optimizer launches), or

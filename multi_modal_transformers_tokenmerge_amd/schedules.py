@@ -14,6 +14,10 @@ optax mapping (s = the count before the step's advance, as ``optax.scale_by_sche
   end)`` (T counts the warm-up steps too; the value stays at ``end`` from T on);
 * ``WarmupRsqrt(init, peak, W, timescale)``: the Octo recipe, a linear warm-up joined to
   ``peak * sqrt(timescale / (s - W + timescale))``.
+
+The decay of the parameter EMA (AdamW.ema_decay; include/mmt_api.h mmt_adamw_ema) is a schedule of
+the same counter and lives here too: ``EmaDecay`` (the diffusers / Diffusion-Policy ``EMAModel``
+warm-up) and ``ConstantEmaDecay``, with ``to_c()``: the ``mmt_ema_decay_t``.
 """
 from __future__ import annotations
 
@@ -108,3 +112,75 @@ class WarmupRsqrt:
 
 
 Schedule = (Constant, WarmupCosine, WarmupRsqrt)
+
+
+# ---------------------------------------------------------------------- parameter EMA decay
+EMA_CONSTANT, EMA_WARMUP = 0, 1  # include/mmt_api.h MMT_EMA_*
+
+
+class EmaDecayC(ctypes.Structure):
+    """mmt_ema_decay_t (include/mmt_api.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("value", ctypes.c_double),
+                ("max_value", ctypes.c_double), ("min_value", ctypes.c_double),
+                ("inv_gamma", ctypes.c_double), ("power", ctypes.c_double),
+                ("update_after_step", ctypes.c_int64)]
+
+
+def _check_unit(name: str, what: str, v: float):
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{name}: {what} {v} outside [0, 1]")
+
+
+@dataclass(frozen=True)
+class EmaDecay:
+    """The decay of the parameter EMA (AdamW.ema_decay), evaluated on the device from the step
+    counter (include/mmt_api.h mmt_adamw_ema, MMT_EMA_WARMUP): the warm-up rule of diffusers'
+    ``EMAModel(decay=max_value, min_decay=min_value, inv_gamma=, power=, update_after_step=,
+    use_ema_warmup=True)`` and of Diffusion Policy's ``EMAModel``. With s the count before the
+    step's advance (as the learning-rate schedules take it) and k = max(0, s - update_after_step
+    - 1): 0 if k == 0, else min(max_value, max(min_value, 1 - (1 + k / inv_gamma)^-power)).
+    ``__call__`` restates it in float64."""
+    max_value: float = 0.9999
+    min_value: float = 0.0
+    inv_gamma: float = 1.0
+    power: float = 0.75
+    update_after_step: int = 0
+
+    def __post_init__(self):
+        _check_unit("EmaDecay", "max_value", self.max_value)
+        _check_unit("EmaDecay", "min_value", self.min_value)
+        if self.min_value > self.max_value:
+            raise ValueError(f"EmaDecay: min_value {self.min_value} > max_value {self.max_value}")
+        if not self.inv_gamma > 0:
+            raise ValueError(f"EmaDecay: inv_gamma {self.inv_gamma} <= 0")
+        if not self.power >= 0:
+            raise ValueError(f"EmaDecay: power {self.power} < 0")
+        if self.update_after_step < 0:
+            raise ValueError(f"EmaDecay: update_after_step {self.update_after_step} < 0")
+
+    def __call__(self, step: int) -> float:
+        k = max(0, step - self.update_after_step - 1)
+        if k == 0:
+            return 0.0
+        d = 1.0 - (1.0 + k / self.inv_gamma) ** -self.power
+        return min(self.max_value, max(self.min_value, d))
+
+    def to_c(self) -> EmaDecayC:
+        return EmaDecayC(kind=EMA_WARMUP, max_value=float(self.max_value),
+                         min_value=float(self.min_value), inv_gamma=float(self.inv_gamma),
+                         power=float(self.power), update_after_step=int(self.update_after_step))
+
+
+@dataclass(frozen=True)
+class ConstantEmaDecay:
+    """A fixed decay in [0, 1] (what a float AdamW.ema_decay becomes): MMT_EMA_CONSTANT."""
+    value: float
+
+    def __post_init__(self):
+        _check_unit("ConstantEmaDecay", "value", self.value)
+
+    def __call__(self, step: int) -> float:
+        return float(self.value)
+
+    def to_c(self) -> EmaDecayC:
+        return EmaDecayC(kind=EMA_CONSTANT, value=float(self.value))

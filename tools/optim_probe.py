@@ -12,6 +12,13 @@
   the 10th..90th percentile spread. The buffers (18 B of state + 4 B of gradient per parameter, 0.4 GB at
   22.5 M) exceed the 256 MB Infinity Cache, so the launches stream from HBM as in a training
   step.
+* parameter EMA: mmt_adamw_ema (constant decay 0.999) in its three forms, "host" (mmt_adamw's
+  arguments), "opt" (mmt_adamw_dev's) and "groups" (mmt_adamw_groups' with the "kernels" table),
+  and the unfused alternative, mmt_adamw followed by ``ema.lerp_(p, 1 - d)``; by bytes 38 B per
+  parameter against AdamW's 30 B (1.27x), the unfused pair 42 B.
+* --yardstick LIB: a second build of the library (e.g. the parent commit's libmmt_hip.so), whose
+  mmt_adamw / mmt_adamw_dev / mmt_adamw_groups[none] are timed in the same rotation as
+  "yardstick:<name>": the same box, the same process, interleaved.
 * --step: ms per step of distributed.DDPStep's one-graph step at the bench configuration with
   the default AdamW(), with a warm-up-cosine schedule + clipping + skip_nonfinite, and with
   AdamW(frozen_keys="head_only") (the backward stops at the heads), the step objects alternating
@@ -36,7 +43,8 @@ sys.path.insert(0, ROOT)
 from multi_modal_transformers_tokenmerge_amd import _C  # noqa: E402
 from multi_modal_transformers_tokenmerge_amd.models.octo.config import get_config  # noqa: E402
 from multi_modal_transformers_tokenmerge_amd.models.octo import octo as O  # noqa: E402
-from multi_modal_transformers_tokenmerge_amd.schedules import WarmupCosine  # noqa: E402
+from multi_modal_transformers_tokenmerge_amd.schedules import (ConstantEmaDecay,  # noqa: E402
+                                                               WarmupCosine)
 
 HYPER = (0.9, 0.999, 1e-8, 1e-4)
 HBM_PEAK_GBS = 8000.0  # MI355X (MI355X_MICROARCH.md, chip table)
@@ -64,7 +72,17 @@ def _stats(us):
                 p90_us=round(float(np.percentile(a, 90)), 2))
 
 
-def probe_kernels(n: int, tables: dict, dev, rounds: int, inner: int, warm: int) -> dict:
+def load_yardstick(path: str):
+    """A second build of the C ABI, bound for the three AdamW launches only."""
+    h = ctypes.CDLL(os.path.abspath(path))
+    for name in ("mmt_adamw", "mmt_adamw_dev", "mmt_adamw_groups"):
+        fn = getattr(h, name)
+        fn.argtypes, fn.restype = _C.SIGNATURES[name], ctypes.c_int
+    return h
+
+
+def probe_kernels(n: int, tables: dict, dev, rounds: int, inner: int, warm: int,
+                  yard=None) -> dict:
     gen = torch.Generator(device=dev).manual_seed(0)
     p = torch.randn(n, generator=gen, device=dev)
     g = torch.randn(n, generator=gen, device=dev) * 1e-2
@@ -105,6 +123,35 @@ def probe_kernels(n: int, tables: dict, dev, rounds: int, inner: int, warm: int)
     for k, t in flags.items():
         variants[f"mmt_adamw_groups[{k}]"] = adamw_groups(t)
         variants[f"mmt_optim_prepare_groups[{k}]"] = prepare_groups(t)
+
+    # parameter EMA: the fused launch in its three forms, and AdamW + a torch pass
+    ema = p.clone()
+    decay = ConstantEmaDecay(0.999).to_c()
+
+    def adamw_ema(o, t):
+        return lambda: _C.call("mmt_adamw_ema", _C.ptr(p), _C.ptr(g), _C.ptr(m), _C.ptr(v),
+                               _C.ptr(shadow), _C.ptr(ema), n, _C.ptr(state), _C.ptr(o), 3e-4,
+                               *HYPER, 1.0, _C.ptr(t), 64, ctypes.addressof(decay), s)
+
+    def unfused():
+        adamw()
+        ema.lerp_(p, 1.0 - 0.999)
+
+    variants["mmt_adamw_ema[host]"] = adamw_ema(None, None)
+    variants["mmt_adamw_ema[opt]"] = adamw_ema(opt, None)
+    variants["mmt_adamw_ema[groups]"] = adamw_ema(None, flags["kernels"])
+    variants["mmt_adamw+lerp"] = unfused
+    if yard is not None:
+        none = flags["none"]
+        variants["yardstick:mmt_adamw"] = lambda: yard.mmt_adamw(
+            _C.ptr(p), _C.ptr(g), _C.ptr(m), _C.ptr(v), _C.ptr(shadow), n, _C.ptr(state), 3e-4,
+            *HYPER, 1.0, s)
+        variants["yardstick:mmt_adamw_dev"] = lambda: yard.mmt_adamw_dev(
+            _C.ptr(p), _C.ptr(g), _C.ptr(m), _C.ptr(v), _C.ptr(shadow), n, _C.ptr(state),
+            _C.ptr(opt), *HYPER, s)
+        variants["yardstick:mmt_adamw_groups[none]"] = lambda: yard.mmt_adamw_groups(
+            _C.ptr(p), _C.ptr(g), _C.ptr(m), _C.ptr(v), _C.ptr(shadow), n, _C.ptr(state), None,
+            3e-4, *HYPER, 1.0, _C.ptr(none), 64, s)
     prepare()  # opt holds a learning rate and a clip factor before the first mmt_adamw_dev
     for fn in variants.values():
         for _ in range(warm):
@@ -142,6 +189,23 @@ def probe_kernels(n: int, tables: dict, dev, rounds: int, inner: int, warm: int)
     out["adamw_groups[none]_inside_adamw_p10_p90"] = bool(base["p10_us"] <= a <= base["p90_us"])
     q = out["mmt_optim_prepare_groups[none]"]["median_us"]
     out["prepare_groups[none]_inside_prepare_p10_p90"] = bool(prep["p10_us"] <= q <= prep["p90_us"])
+    # the EMA launches against the yardstick: the other build's mmt_adamw if one was given, else
+    # this build's; accepted up to the byte ratio 38 / 30 plus the yardstick's own spread
+    ref = out.get("yardstick:mmt_adamw", base)
+    spread = (ref["p90_us"] - ref["p10_us"]) / ref["median_us"]
+    out["ema_yardstick"] = "yardstick:mmt_adamw" if yard is not None else "mmt_adamw"
+    out["ema_yardstick_spread_rel"] = round(spread, 4)
+    out["ema_accept_ratio"] = round(38.0 / 30.0 + spread, 4)
+    for k in ("mmt_adamw_ema[host]", "mmt_adamw_ema[opt]", "mmt_adamw_ema[groups]",
+              "mmt_adamw+lerp"):
+        out[f"{k}_over_yardstick"] = round(out[k]["median_us"] / ref["median_us"], 4)
+    out["adamw_ema_gbs"] = round(38.0 * n / out["mmt_adamw_ema[host]"]["median_us"] / 1e3, 1)
+    out["adamw_ema_within_byte_ratio"] = bool(
+        out["mmt_adamw_ema[host]_over_yardstick"] <= out["ema_accept_ratio"])
+    if yard is not None:  # the unchanged entry points against the other build's
+        for k in ("mmt_adamw", "mmt_adamw_dev", "mmt_adamw_groups[none]"):
+            out[f"{k}_over_yardstick"] = round(
+                out[k]["median_us"] / out[f"yardstick:{k}"]["median_us"], 4)
     return out
 
 
@@ -201,6 +265,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=42)
     ap.add_argument("--inner", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--yardstick", default=None, metavar="LIB",
+                    help="a second build of libmmt_hip.so to time in the same rotation")
     ap.add_argument("--step", action="store_true", help="also time the graphed train step")
     ap.add_argument("--step-config", default="octo-small-tome16")
     ap.add_argument("--batch", type=int, default=512)
@@ -213,10 +279,11 @@ def main():
     torch.cuda.set_device(dev)
     res = {"device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "inner": args.inner,
            "kernels": {}}
+    yard = load_yardstick(args.yardstick) if args.yardstick else None
     for c in args.configs:
         n, tables = flat_count(c)
         res["kernels"][c] = dict(n=n, **probe_kernels(n, tables, dev, args.rounds, args.inner,
-                                                      args.warmup))
+                                                      args.warmup, yard))
     if args.step:
         res["step"] = dict(config=args.step_config, batch=args.batch, steps=args.steps,
                            **probe_step(args.step_config, args.batch, dev, args.steps,
