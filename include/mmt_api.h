@@ -146,7 +146,9 @@ int mmt_ln_unmerge_dropout_bwd(const void* dy, int64_t ds_b, int64_t ds_t, const
 /* mmt_tome_merge_wavg_fwd fused with the sequence-axis LayerNorm forward that follows it in the
  * block (attention.py:66; mmt_seqnorm_fwd semantics): fp32 x, merged rows x_out (bit-identical to
  * the unfused merge), size_out / pos_map as there, y = LN(x_out) bf16 with mean / rstd (B, D)
- * (bit-identical to mmt_seqnorm_fwd on x_out). L - r <= 512, D % 8 == 0. */
+ * (bit-identical to mmt_seqnorm_fwd on x_out). L - r <= 512, D % 8 == 0. Both fused entries
+ * follow the operand rules of the sequence LayerNorm section below and report their kernel form
+ * through mmt_norm_last_route(). */
 int mmt_tome_merge_seqnorm_fwd(const float* x, int n, int L, int D, int64_t x_s_n, int64_t x_s_t,
                                int set_start, int t, int r, int flags, const float* size_in,
                                const int32_t* unm_idx, const int32_t* src_idx,
@@ -478,7 +480,36 @@ int mmt_dropout_bits(const uint32_t* rng, uint32_t layer, uint32_t site, int row
  * attention.py:58,66 (vanilla_decoder.yaml:5-13): stats per (b, d) over the SEQUENCE axis L,
  * fast variance; x (B, L, D) strided, bf16 or fp32 (x_dtype; the training path keeps the residual
  * stream in fp32 because this normalisation subtracts a large per-feature sequence mean); y bf16;
- * mean/rstd fp32 (B, D) saved for the backward. */
+ * mean/rstd fp32 (B, D) saved for the backward.
+ * Operand rules, the same for the five entry points of the family (mmt_seqnorm_fwd,
+ * mmt_seqnorm_bwd, mmt_seqnorm_dropout_bwd, mmt_ln_unmerge_dropout_bwd and
+ * mmt_tome_merge_seqnorm_fwd), checked before anything is launched (MMT_ERR_INVALID): every
+ * (B, L, D) operand (x, y, dy, addend, dx, z, g_in, x_out) is moved as 16-B vectors, so its base
+ * pointer is 16-B aligned, its row and batch strides are multiples of 8 elements and its row
+ * stride is at least D; B, L, D > 0 and D % 8 == 0. addend is optional (NULL: its strides are
+ * ignored). mean, rstd (B, D), gamma, beta, dgamma, dbeta, colsum / bias_grad [D] are contiguous
+ * fp32 read and written one element at a time. Nothing outside rows [0, L) x columns [0, D) of a
+ * sample is read or written; dgamma, dbeta and the column sums are ACCUMULATED at [0, D). */
+/* The kernel form that the last call of one of those five entry points launched:
+ * MMT_NORM_ROUTE_NONE after a call rejected before any launch, else the entry point's code, the
+ * rows per thread of the register-resident form MMT_NORM_ROUTE_RPT (4 / 6 / 8 / 10 for
+ * L <= 128 / 192 / 256 / 320 rows — L2 of mmt_ln_unmerge_dropout_bwd, L - r of
+ * mmt_tome_merge_seqnorm_fwd — taken only for fp32 x with bf16 dy; 0: the two-pass form, also
+ * with MMT_SNB_RPT=0 in the environment), and MMT_NORM_ROUTE_X_BF16 / _DY_BF16 for the operand
+ * types (dy: the backward entries). Process-wide, not thread-safe. */
+enum {
+  MMT_NORM_ROUTE_NONE = 0,
+  MMT_NORM_ROUTE_SEQ_FWD = 1,         /* mmt_seqnorm_fwd: seqnorm_fwd_kernel */
+  MMT_NORM_ROUTE_SEQ_BWD = 2,         /* mmt_seqnorm_bwd: seqnorm_bwd_kernel */
+  MMT_NORM_ROUTE_SEQ_DROPOUT_BWD = 3, /* mmt_seqnorm_dropout_bwd: seqnorm_bwd_kernel<DZ> */
+  MMT_NORM_ROUTE_LN_UNMERGE_BWD = 4,  /* mmt_ln_unmerge_dropout_bwd */
+  MMT_NORM_ROUTE_MERGE_SEQ_FWD = 5,   /* mmt_tome_merge_seqnorm_fwd */
+  MMT_NORM_ROUTE_ENTRY_MASK = 0xff,
+  MMT_NORM_ROUTE_X_BF16 = 0x10000,
+  MMT_NORM_ROUTE_DY_BF16 = 0x20000
+};
+#define MMT_NORM_ROUTE_RPT(route) (((route) >> 8) & 0xf)
+int mmt_norm_last_route(void);
 int mmt_seqnorm_fwd(const void* x, int x_dtype, int64_t xs_b, int64_t xs_t, int B, int L, int D,
                     const float* gamma, const float* beta, float eps, void* y, int64_t ys_b,
                     int64_t ys_t, float* mean, float* rstd, mmt_stream_t stream);

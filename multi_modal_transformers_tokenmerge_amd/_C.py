@@ -45,6 +45,7 @@ SIGNATURES: dict[str, list] = {
     "mmt_gemm_set_variant": [I],
     "mmt_gemm_last_route": [],
     "mmt_attn_last_route": [],
+    "mmt_norm_last_route": [],
     "mmt_set_deterministic": [P, P, L],
     "mmt_det_flush": [P, P, L, P],
     "mmt_gemm_colsum_rows": [I, I, I, I, I, I, I],
@@ -121,6 +122,7 @@ _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: erro
             "mmt_gemm_colsum_rows": I,    # returns a row count
             "mmt_gemm_last_route": I,     # returns a ROUTE_* value
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
+            "mmt_norm_last_route": I,     # returns a NORM_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -223,6 +225,23 @@ def attn_route(kernel: int, param: int, dh: int = 0, worklist: bool = False) -> 
 
 def attn_last_route() -> int:
     return call("mmt_attn_last_route")
+
+
+# MMT_NORM_ROUTE_* (include/mmt_api.h): what mmt_norm_last_route() reports
+(NORM_ROUTE_NONE, NORM_ROUTE_SEQ_FWD, NORM_ROUTE_SEQ_BWD, NORM_ROUTE_SEQ_DROPOUT_BWD,
+ NORM_ROUTE_LN_UNMERGE_BWD, NORM_ROUTE_MERGE_SEQ_FWD) = range(6)
+NORM_ROUTE_ENTRY_MASK, NORM_ROUTE_X_BF16, NORM_ROUTE_DY_BF16 = 0xff, 0x10000, 0x20000
+
+
+def norm_route(entry: int, rpt: int, x_bf16: bool = False, dy_bf16: bool = False) -> int:
+    """The route of `entry` in the form with `rpt` rows per thread (MMT_NORM_ROUTE_RPT; 0: the
+    two-pass form) and the operand types."""
+    return (entry | rpt << 8 | (NORM_ROUTE_X_BF16 if x_bf16 else 0)
+            | (NORM_ROUTE_DY_BF16 if dy_bf16 else 0))
+
+
+def norm_last_route() -> int:
+    return call("mmt_norm_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

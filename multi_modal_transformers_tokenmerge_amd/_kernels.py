@@ -102,27 +102,32 @@ def tome_merge_fwd(x: torch.Tensor, set_start: int, t: int, r: int, unm, src, ds
 
 def tome_merge_seqnorm_fwd(x: torch.Tensor, set_start: int, t: int, r: int, unm, src, dst,
                            gamma: torch.Tensor, beta: torch.Tensor, eps: float,
-                           size_in: torch.Tensor | None = None, flags: int = 0):
+                           size_in: torch.Tensor | None = None, flags: int = 0,
+                           out: torch.Tensor | None = None, y_out: torch.Tensor | None = None,
+                           mean_out: torch.Tensor | None = None,
+                           rstd_out: torch.Tensor | None = None):
     """tome_merge_fwd (fp32 x) followed by seqnorm_fwd in one launch: returns (x_out, size_out,
-    pos_map, y bf16, mean, rstd), each bit-identical to the two-launch form."""
-    _dev(x, size_in, unm, src, dst, gamma, beta)
+    pos_map, y bf16, mean, rstd), each bit-identical to the two-launch form. out / y_out /
+    mean_out / rstd_out: optional destinations of x_out / y (strided views allowed) and the
+    statistics."""
+    _dev(x, size_in, unm, src, dst, gamma, beta, out, y_out, mean_out, rstd_out)
     n, L, D = x.shape
     if x.dtype != torch.float32 or x.stride(2) != 1:
         raise ValueError("tome_merge_seqnorm_fwd takes an fp32 (n, L, D) sequence, unit stride along D")
-    if not (0 <= set_start and set_start + t <= L) or L - r > 512:
-        raise ValueError("token set out of range or sequence too long for the fused form")
+    if not (0 <= set_start and set_start + t <= L):  # (L - r <= 512 is the library's check)
+        raise ValueError("token set out of range")
     for a, shape in ((unm, (n, (t + 1) // 2 - r)), (src, (n, r)), (dst, (n, r))):
         if tuple(a.shape) != shape or a.dtype != torch.int32 or not a.is_contiguous():
             raise ValueError(f"index tensor must be contiguous int32 {shape}")
     if size_in is not None and (tuple(size_in.shape) != (n, t) or size_in.dtype != torch.float32
                                 or not size_in.is_contiguous()):
         raise ValueError("size_in must be contiguous fp32 (n, t)")
-    out = torch.empty((n, L - r, D), dtype=torch.float32, device=x.device)
+    out = _seq_out(out, (n, L - r, D), torch.float32, x.device, "out")
     size_out = torch.empty((n, t - r), dtype=torch.float32, device=x.device)
     pos_map = torch.empty((n, t), dtype=torch.int32, device=x.device)
-    y = torch.empty((n, L - r, D), dtype=torch.bfloat16, device=x.device)
-    mean = torch.empty((n, D), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((n, D), dtype=torch.float32, device=x.device)
+    y = _seq_out(y_out, (n, L - r, D), torch.bfloat16, x.device, "y_out")
+    mean = _stat_out(mean_out, n, D, x.device, "mean_out")
+    rstd = _stat_out(rstd_out, n, D, x.device, "rstd_out")
     _C.call("mmt_tome_merge_seqnorm_fwd", ptr(x), n, L, D, x.stride(0), x.stride(1), set_start, t,
             r, flags, ptr(size_in), ptr(unm), ptr(src), ptr(dst), ptr(out), out.stride(0),
             out.stride(1), ptr(size_out), ptr(pos_map), ptr(gamma), ptr(beta), eps, ptr(y),
@@ -662,15 +667,34 @@ def tome_size_bias(B: int, L: int, sets, out: torch.Tensor | None = None) -> tor
 
 
 # ------------------------------------------------------------------------ seq LayerNorm etc.
+def _seq_out(out, shape, dtype, device, what: str):
+    """`out` or a fresh (B, L, D) tensor; a given one may be a strided view (unit stride along D)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.stride(-1) != 1:
+        raise ValueError(f"{what} must be {dtype} {tuple(shape)} with unit stride along D")
+    return out
+
+
+def _stat_out(out, B: int, D: int, device, what: str):
+    """`out` or a fresh contiguous fp32 (B, D) tensor (mean / rstd)."""
+    if out is None:
+        return torch.empty((B, D), dtype=torch.float32, device=device)
+    if tuple(out.shape) != (B, D) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"{what} must be contiguous fp32 {(B, D)}")
+    return out
+
+
 def seqnorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
-                out: torch.Tensor | None = None):
+                out: torch.Tensor | None = None, mean_out: torch.Tensor | None = None,
+                rstd_out: torch.Tensor | None = None):
     """x (B, L, D) bf16 or fp32 (the residual stream) -> y bf16, mean, rstd (B, D) fp32."""
-    _dev(x, gamma, beta, out)
+    _dev(x, gamma, beta, out, mean_out, rstd_out)
     B, L, D = x.shape
     if out is None:
         out = torch.empty((B, L, D), dtype=torch.bfloat16, device=x.device)
-    mean = torch.empty((B, D), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    mean = _stat_out(mean_out, B, D, x.device, "mean_out")
+    rstd = _stat_out(rstd_out, B, D, x.device, "rstd_out")
     _C.call("mmt_seqnorm_fwd", ptr(x), _dtype_code(x), x.stride(0), x.stride(1), B, L, D,
             ptr(gamma), ptr(beta), eps, ptr(out), out.stride(0), out.stride(1), ptr(mean),
             ptr(rstd), _C.stream_ptr())
@@ -701,15 +725,17 @@ def colsum(x2d: torch.Tensor, out: torch.Tensor):
 
 
 def seqnorm_dropout_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, rng, layer: int,
-                        site: int, keep_prob: float, row_offset: int, colsum=None):
+                        site: int, keep_prob: float, row_offset: int, colsum=None, out=None,
+                        z_out=None):
     """seqnorm_bwd (bf16 dy, fp32 x / addend) returning (dx fp32, z bf16), z = the previous
-    block's dropout backward of dx (dropout_bwd semantics, colsum += its column sums)."""
-    _dev(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, rng, colsum)
+    block's dropout backward of dx (dropout_bwd semantics, colsum += its column sums).
+    out / z_out: optional (strided) destinations of dx / z."""
+    _dev(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, rng, colsum, out, z_out)
     B, L, D = x.shape
     if x.dtype != torch.float32 or dy.dtype != torch.bfloat16 or (addend is not None and addend.dtype != torch.float32):
         raise TypeError("seqnorm_dropout_bwd takes bf16 dy and fp32 x / addend")
-    dx = torch.empty((B, L, D), dtype=torch.float32, device=x.device)
-    z = torch.empty((B, L, D), dtype=torch.bfloat16, device=x.device)
+    dx = _seq_out(out, (B, L, D), torch.float32, x.device, "out")
+    z = _seq_out(z_out, (B, L, D), torch.bfloat16, x.device, "z_out")
     a_sb, a_st = (addend.stride(0), addend.stride(1)) if addend is not None else (0, 0)
     _C.call("mmt_seqnorm_dropout_bwd", ptr(dy), dy.stride(0), dy.stride(1), ptr(x), x.stride(0),
             x.stride(1), B, L, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(addend), a_sb, a_st, ptr(dx),
@@ -730,18 +756,20 @@ def ln_unmerge_ok(L: int, L2: int) -> bool:
 
 
 def ln_unmerge_dropout_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, tome, rng, layer: int,
-                           site: int, keep_prob: float, row_offset: int, bias_grad=None):
+                           site: int, keep_prob: float, row_offset: int, bias_grad=None, out=None,
+                           z_out=None):
     """seqnorm_bwd (merged layout: dy bf16, x / addend fp32) -> tome_merge_bwd -> dropout_bwd in one
     launch: returns (g_in fp32 (B, L, D), z bf16 (B, L, D)); dgamma / dbeta / bias_grad accumulated.
-    tome = (set_start, t, r, pos_map, size_in, size_out)."""
-    _dev(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, rng, bias_grad)
+    tome = (set_start, t, r, pos_map, size_in, size_out). out / z_out: optional (strided)
+    destinations of g_in / z."""
+    _dev(dy, x, mean, rstd, gamma, dgamma, dbeta, addend, rng, bias_grad, out, z_out)
     B, L2, D = x.shape
     s0, t, r, pos, size_in, size_out = tome
     L = L2 + r
     if x.dtype != torch.float32 or dy.dtype != torch.bfloat16 or (addend is not None and addend.dtype != torch.float32):
         raise TypeError("ln_unmerge_dropout_bwd takes bf16 dy and fp32 x / addend")
-    g_in = torch.empty((B, L, D), dtype=torch.float32, device=x.device)
-    z = torch.empty((B, L, D), dtype=torch.bfloat16, device=x.device)
+    g_in = _seq_out(out, (B, L, D), torch.float32, x.device, "out")
+    z = _seq_out(z_out, (B, L, D), torch.bfloat16, x.device, "z_out")
     a_sb, a_st = (addend.stride(0), addend.stride(1)) if addend is not None else (0, 0)
     _C.call("mmt_ln_unmerge_dropout_bwd", ptr(dy), dy.stride(0), dy.stride(1), ptr(x), x.stride(0),
             x.stride(1), B, L2, D, ptr(mean), ptr(rstd), ptr(gamma), ptr(addend), a_sb, a_st,

@@ -120,6 +120,19 @@ __device__ __forceinline__ int ln_sample() { return MMT_LN_COLFIRST ? blockIdx.y
 __device__ __forceinline__ int ln_colblk() { return MMT_LN_COLFIRST ? blockIdx.x : blockIdx.y; }
 inline dim3 ln_grid(int n, int cblocks) { return MMT_LN_COLFIRST ? dim3(cblocks, n) : dim3(n, cblocks); }
 
+// The kernel form of the last sequence-LN launch (MMT_NORM_ROUTE_*, include/mmt_api.h;
+// mmt_norm_last_route): set by the five entry points of norm.hip and tome.hip, MMT_NORM_ROUTE_NONE
+// after a call rejected before its launch. Defined in core.hip. Process-wide, not thread-safe.
+extern int g_norm_route;
+inline int norm_route(int entry, int rpt, bool x_bf16, bool dy_bf16) {
+  return entry | rpt << 8 | (x_bf16 ? MMT_NORM_ROUTE_X_BF16 : 0) | (dy_bf16 ? MMT_NORM_ROUTE_DY_BF16 : 0);
+}
+// One (B, L, D) operand of the family, moved as 16-B vectors: the base 16-B aligned, the row and
+// batch strides multiples of 8 elements, a row stride that covers the D columns of a row.
+inline bool ln_operand_ok(const void* p, int64_t s_b, int64_t s_t, int D) {
+  return ((uintptr_t)p & 15) == 0 && s_b % 8 == 0 && s_t % 8 == 0 && s_t >= D;
+}
+
 // ---------------------------------------------------------------- wave helpers (wave64)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -542,18 +542,21 @@ static int snb_rpt(int L) {
   return 0;
 }
 
-
 extern "C" int mmt_seqnorm_fwd(const void* x, int x_dtype, int64_t xs_b, int64_t xs_t, int B,
                                int L, int D, const float* gamma, const float* beta, float eps,
                                void* y, int64_t ys_b, int64_t ys_t, float* mean, float* rstd,
                                mmt_stream_t stream) {
+  g_norm_route = MMT_NORM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(x && y && gamma && beta && mean && rstd, "mmt_seqnorm_fwd: null pointer");
   MMT_CHECK_ARG(is_dt(x_dtype), "mmt_seqnorm_fwd: x_dtype");
   MMT_CHECK_ARG(B > 0 && L > 0 && D > 0 && D % 8 == 0 && xs_t % 8 == 0 && ys_t % 8 == 0 &&
                     xs_b % 8 == 0 && ys_b % 8 == 0,
                 "mmt_seqnorm_fwd: D and strides must be multiples of 8");
+  MMT_CHECK_ARG(ln_operand_ok(x, xs_b, xs_t, D) && ln_operand_ok(y, ys_b, ys_t, D),
+                "mmt_seqnorm_fwd: x and y need 16-B aligned bases and row strides >= D");
   const dim3 grid = ln_grid(B, (D + CW - 1) / CW);
-  const int rpt = snb_rpt(L);
+  const int rpt = x_dtype == MMT_F32 ? snb_rpt(L) : 0;
+  g_norm_route = norm_route(MMT_NORM_ROUTE_SEQ_FWD, rpt, x_dtype == MMT_BF16, false);
   if (x_dtype == MMT_F32 && rpt) {
 #define SNF(R)                                                                                       \
   hipLaunchKernelGGL((seqnorm_fwd_kernel<float, R>), grid, dim3(NT), 0, as_stream(stream),          \
@@ -582,19 +585,26 @@ extern "C" int mmt_seqnorm_bwd(const void* dy, int dy_dtype, int64_t ds_b, int64
                                const float* gamma, const void* addend, int64_t as_b, int64_t as_t,
                                void* dx, int64_t dxs_b, int64_t dxs_t, float* dgamma, float* dbeta,
                                mmt_stream_t stream) {
+  g_norm_route = MMT_NORM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta,
                 "mmt_seqnorm_bwd: null pointer");
   MMT_CHECK_ARG(is_dt(dy_dtype) && is_dt(x_dtype), "mmt_seqnorm_bwd: dtypes");
   MMT_CHECK_ARG(B > 0 && L > 0 && D > 0 && D % 8 == 0 && ds_t % 8 == 0 && xs_t % 8 == 0 &&
-                    dxs_t % 8 == 0 && (!addend || as_t % 8 == 0),
+                    dxs_t % 8 == 0 && (!addend || as_t % 8 == 0) && ds_b % 8 == 0 &&
+                    xs_b % 8 == 0 && dxs_b % 8 == 0 && (!addend || as_b % 8 == 0),
                 "mmt_seqnorm_bwd: D and strides must be multiples of 8");
+  MMT_CHECK_ARG(ln_operand_ok(dy, ds_b, ds_t, D) && ln_operand_ok(x, xs_b, xs_t, D) &&
+                    ln_operand_ok(dx, dxs_b, dxs_t, D) &&
+                    (!addend || ln_operand_ok(addend, as_b, as_t, D)),
+                "mmt_seqnorm_bwd: dy, x, addend and dx need 16-B aligned bases and row strides >= D");
   const dim3 grid = ln_grid(B, (D + CW - 1) / CW);
   hipStream_t s = as_stream(stream);
 #define SNB(TDY, TX)                                                                             \
   hipLaunchKernelGGL((seqnorm_bwd_kernel<TDY, TX>), grid, dim3(NT), 0, s, (const TDY*)dy, ds_b, \
                      ds_t, (const TX*)x, xs_b, xs_t, L, D, mean, rstd, gamma, (const TX*)addend,  \
                      as_b, as_t, (TX*)dx, dxs_b, dxs_t, dgamma, dbeta)
-  const int rpt = snb_rpt(L);
+  const int rpt = dy_dtype == MMT_BF16 && x_dtype == MMT_F32 ? snb_rpt(L) : 0;
+  g_norm_route = norm_route(MMT_NORM_ROUTE_SEQ_BWD, rpt, x_dtype == MMT_BF16, dy_dtype == MMT_BF16);
   if (dy_dtype == MMT_BF16 && x_dtype == MMT_F32 && rpt) {
 #define SNBR(R)                                                                                     \
   hipLaunchKernelGGL((seqnorm_bwd_kernel<bf16_t, float, false, R>), grid, dim3(NT), 0, s,           \
@@ -661,6 +671,7 @@ extern "C" int mmt_ln_unmerge_dropout_bwd(
     const float* size_in, const float* size_out, const int32_t* pos_map, float* g_in, int64_t gs_b,
     int64_t gs_t, const uint32_t* rng, uint32_t layer, uint32_t site, float keep_prob,
     int64_t row_offset, void* z, int64_t zs_b, int64_t zs_t, float* bias_grad, mmt_stream_t stream) {
+  g_norm_route = MMT_NORM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(dy && x && mean && rstd && gamma && dgamma && dbeta && pos_map && g_in && z,
                 "mmt_ln_unmerge_dropout_bwd: null pointer");
   MMT_CHECK_ARG(B > 0 && L2 > 0 && D > 0 && D % 8 == 0 && L == L2 + r && r > 0 && t >= 2 &&
@@ -668,13 +679,20 @@ extern "C" int mmt_ln_unmerge_dropout_bwd(
                     L2 * CW * 4 <= 96 * 1024,
                 "mmt_ln_unmerge_dropout_bwd: bad shape (L <= %d)", kUnmergeMax);
   MMT_CHECK_ARG(ds_t % 8 == 0 && xs_t % 8 == 0 && gs_t % 8 == 0 && zs_t % 8 == 0 &&
-                    (!addend || as_t % 8 == 0),
+                    (!addend || as_t % 8 == 0) && ds_b % 8 == 0 && xs_b % 8 == 0 &&
+                    gs_b % 8 == 0 && zs_b % 8 == 0 && (!addend || as_b % 8 == 0),
                 "mmt_ln_unmerge_dropout_bwd: strides must be multiples of 8");
+  MMT_CHECK_ARG(ln_operand_ok(dy, ds_b, ds_t, D) && ln_operand_ok(x, xs_b, xs_t, D) &&
+                    ln_operand_ok(g_in, gs_b, gs_t, D) && ln_operand_ok(z, zs_b, zs_t, D) &&
+                    (!addend || ln_operand_ok(addend, as_b, as_t, D)),
+                "mmt_ln_unmerge_dropout_bwd: dy, x, addend, g_in and z need 16-B aligned bases "
+                "and row strides >= D");
   MMT_CHECK_ARG(!rng || (keep_prob > 0.f && keep_prob <= 1.f), "mmt_ln_unmerge_dropout_bwd: keep_prob");
   const int cwt = CW;
   const size_t dyn = sizeof(float) * (size_t)std::max(L2 * cwt, 4 * (NT / (cwt / 8)) * cwt);
   const dim3 grid = ln_grid(B, (D + cwt - 1) / cwt);
   const int rpt = snb_rpt(L2);
+  g_norm_route = norm_route(MMT_NORM_ROUTE_LN_UNMERGE_BWD, rpt, false, true);
 #define LUD(R, CWV)                                                                                 \
   do {                                                                                              \
     static const bool attr_ = (hipFuncSetAttribute((const void*)ln_unmerge_dropout_bwd_kernel<R, CWV>, \
@@ -706,17 +724,26 @@ extern "C" int mmt_seqnorm_dropout_bwd(const void* dy, int64_t ds_b, int64_t ds_
                                        const uint32_t* rng, uint32_t layer, uint32_t site,
                                        float keep_prob, int64_t row_offset, void* z, int64_t zs_b,
                                        int64_t zs_t, float* colsum, mmt_stream_t stream) {
+  g_norm_route = MMT_NORM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && z,
                 "mmt_seqnorm_dropout_bwd: null pointer");
   MMT_CHECK_ARG(B > 0 && L > 0 && D > 0 && D % 8 == 0 && ds_t % 8 == 0 && xs_t % 8 == 0 &&
-                    dxs_t % 8 == 0 && zs_t % 8 == 0 && (!addend || as_t % 8 == 0),
+                    dxs_t % 8 == 0 && zs_t % 8 == 0 && (!addend || as_t % 8 == 0) &&
+                    ds_b % 8 == 0 && xs_b % 8 == 0 && dxs_b % 8 == 0 && zs_b % 8 == 0 &&
+                    (!addend || as_b % 8 == 0),
                 "mmt_seqnorm_dropout_bwd: D and strides must be multiples of 8");
+  MMT_CHECK_ARG(ln_operand_ok(dy, ds_b, ds_t, D) && ln_operand_ok(x, xs_b, xs_t, D) &&
+                    ln_operand_ok(dx, dxs_b, dxs_t, D) && ln_operand_ok(z, zs_b, zs_t, D) &&
+                    (!addend || ln_operand_ok(addend, as_b, as_t, D)),
+                "mmt_seqnorm_dropout_bwd: dy, x, addend, dx and z need 16-B aligned bases and "
+                "row strides >= D");
   MMT_CHECK_ARG(!rng || (keep_prob > 0.f && keep_prob <= 1.f), "mmt_seqnorm_dropout_bwd: keep_prob");
   DropZ dz{rng, layer, site, rng ? keep_threshold16(keep_prob) : 0u, rng ? 1.f / keep_prob : 1.f,
            row_offset, (bf16_t*)z, zs_b, zs_t, colsum};
   const dim3 grid = ln_grid(B, (D + CW - 1) / CW);
   const int rpt = snb_rpt(L);
-#define SDZ(R)                                                                                      \
+  g_norm_route = norm_route(MMT_NORM_ROUTE_SEQ_DROPOUT_BWD, rpt, false, true);
+#define SDZ(R)                                                                                     \
   hipLaunchKernelGGL((seqnorm_bwd_kernel<bf16_t, float, true, R>), grid, dim3(NT), 0,               \
                      as_stream(stream), (const bf16_t*)dy, ds_b, ds_t, x, xs_b, xs_t, L, D, mean,   \
                      rstd, gamma, addend, as_b, as_t, dx, dxs_b, dxs_t, dgamma, dbeta, dz)

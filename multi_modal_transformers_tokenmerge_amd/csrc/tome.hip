@@ -1266,6 +1266,7 @@ extern "C" int mmt_tome_merge_seqnorm_fwd(const float* x, int n, int L, int D, i
                                           const float* beta, float eps, void* y, int64_t y_s_n,
                                           int64_t y_s_t, float* mean, float* rstd,
                                           mmt_stream_t stream) {
+  g_norm_route = MMT_NORM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(x && x_out && (unm_idx || (t + 1) / 2 == r) && src_idx && dst_idx && gamma && beta &&
                     y && mean && rstd,
                 "mmt_tome_merge_seqnorm_fwd: null pointer");
@@ -1277,10 +1278,15 @@ extern "C" int mmt_tome_merge_seqnorm_fwd(const float* x, int n, int L, int D, i
   MMT_CHECK_ARG(x_s_t % 8 == 0 && x_s_n % 8 == 0 && o_s_t % 8 == 0 && o_s_n % 8 == 0 &&
                     y_s_t % 8 == 0 && y_s_n % 8 == 0,
                 "mmt_tome_merge_seqnorm_fwd: strides must be multiples of 8");
+  MMT_CHECK_ARG(ln_operand_ok(x, x_s_n, x_s_t, D) && ln_operand_ok(x_out, o_s_n, o_s_t, D) &&
+                    ln_operand_ok(y, y_s_n, y_s_t, D),
+                "mmt_tome_merge_seqnorm_fwd: x, x_out and y need 16-B aligned bases and row "
+                "strides >= D");
   const dim3 grid = ln_grid(n, (D + 63) / 64);
   const int Lo = L - r;
   static const bool rpt_on = !getenv("MMT_SNB_RPT") || atoi(getenv("MMT_SNB_RPT")) != 0;
   const int rpt = !rpt_on ? 0 : Lo <= 128 ? 4 : Lo <= 192 ? 6 : Lo <= 256 ? 8 : Lo <= 320 ? 10 : 0;
+  g_norm_route = norm_route(MMT_NORM_ROUTE_MERGE_SEQ_FWD, rpt, false, false);
 #define TMS(R) hipLaunchKernelGGL((tome_merge_seqnorm_fwd_kernel<R>), grid, dim3(256), 0, as_stream(stream), ARGS_)
   unsigned int* const fault = fault_word();
 #define ARGS_ x, L, D, x_s_n, x_s_t, set_start, t, r, flags, size_in, unm_idx, src_idx, dst_idx, x_out, o_s_n, o_s_t, size_out, pos_map, gamma, beta, eps, (bf16_t*)y, y_s_n, y_s_t, mean, rstd, fault

@@ -96,6 +96,14 @@ int main() {
   invalid(mmt_tome_merge_seqnorm_fwd(fp, 2, 292, 384, 292 * 384, 384, 32, 256, 16, 0, nullptr, ip,
                                      ip, ip, fp, 276 * 384, 384, fp, ip, nullptr, fp, 1e-6f, p,
                                      276 * 384, 384, fp, fp, nullptr), "merge+LN null gamma");
+  invalid(mmt_tome_merge_seqnorm_fwd(fp, 2, 292, 384, 292 * 384, 376, 32, 256, 16, 0, nullptr, ip,
+                                     ip, ip, fp, 276 * 384, 384, fp, ip, fp, fp, 1e-6f, p,
+                                     276 * 384, 384, fp, fp, nullptr), "merge+LN row stride < D");
+  invalid(mmt_tome_merge_seqnorm_fwd(fp + 2, 2, 292, 384, 292 * 384, 384, 32, 256, 16, 0, nullptr,
+                                     ip, ip, ip, fp, 276 * 384, 384, fp, ip, fp, fp, 1e-6f, p,
+                                     276 * 384, 384, fp, fp, nullptr), "merge+LN x not 16-B");
+  EXPECT(mmt_norm_last_route() == MMT_NORM_ROUTE_NONE, "route %d after a rejected merge+LN",
+         mmt_norm_last_route());
   // ---- pruning (token_compression.py:15-46, compressed_attention.py:302-308)
   const int32_t starts[2] = {0, 32}, lens[2] = {32, 256}, ks[2] = {32, 200};
   const int32_t lens_bad[2] = {32, 300};

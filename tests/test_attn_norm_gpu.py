@@ -223,12 +223,15 @@ def test_attention_bias_mode(dev):
                                         (2, 1064, 768, torch.float32)])
 def test_seqnorm(dev, B, L, D, xdt):
     """bf16 and fp32 (the step's residual stream) inputs, L from 1 to 1064, against fp32 torch."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    from tests.seqnorm_ref import expected_rpt
+    xb = xdt == torch.bfloat16
     g = torch.Generator().manual_seed(B + L + D)
     x = (torch.randn((B, L, D), generator=g) * 2 + 0.5).to(xdt).to(dev)
     gamma = torch.randn(D, generator=g).to(dev)
     beta = torch.randn(D, generator=g).to(dev)
     y, mean, rstd = K.seqnorm_fwd(x, gamma, beta, 1e-6)
+    assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_SEQ_FWD, expected_rpt(L, xb), xb)
     xf = x.float().requires_grad_()
     mu = xf.mean(dim=1, keepdim=True)
     var = torch.clamp((xf * xf).mean(dim=1, keepdim=True) - mu * mu, min=0)
@@ -239,6 +242,7 @@ def test_seqnorm(dev, B, L, D, xdt):
     dg = torch.zeros(D, device=dev)
     db = torch.zeros(D, device=dev)
     dx = K.seqnorm_bwd(dy, x, mean, rstd, gamma, dg, db, addend=add)
+    assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_SEQ_BWD, expected_rpt(L, xb), xb, True)
     gam = gamma.clone().requires_grad_()
     bet = beta.clone().requires_grad_()
     ref = (xf - mu) * (torch.rsqrt(var + 1e-6) * gam) + bet
@@ -272,7 +276,8 @@ def test_seqnorm_dropout_bwd_fused(dev, B, L, D, drop):
     """LayerNorm_0 backward fused with the previous block's MLP-output dropout backward, against
     seqnorm_bwd then dropout_bwd: dx and the dropout output bit for bit, the LayerNorm parameter
     gradients and the bias column sums to fp32 atomic-order rounding."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    from tests.seqnorm_ref import expected_rpt
     g = torch.Generator().manual_seed(B * L + D)
     x = (torch.randn((B, L, D), generator=g) * 2 + 0.5).to(dev)
     gamma, beta = torch.randn(D, generator=g).to(dev), torch.randn(D, generator=g).to(dev)
@@ -285,6 +290,8 @@ def test_seqnorm_dropout_bwd_fused(dev, B, L, D, drop):
     a_z = K.dropout_bwd(a_x.reshape(B * L, D), rng, 4, 3, 0.9, row_offset=5 * L, colsum_out=grads[2])
     b_x, b_z = K.seqnorm_dropout_bwd(dy, x, mean, rstd, gamma, grads[3], grads[4], add, rng, 4, 3,
                                      0.9, 5 * L, colsum=grads[5])
+    assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_SEQ_DROPOUT_BWD, expected_rpt(L),
+                                                 dy_bf16=True)
     assert torch.equal(a_x, b_x)
     assert torch.equal(a_z.view(B, L, D), b_z)
     for i in range(3):

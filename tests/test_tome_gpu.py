@@ -153,7 +153,8 @@ def test_reference_api_merge_wavg_autograd(dev):
 def test_merge_seqnorm_fused_bit_exact(dev, n, L, D, s0, t, r, sized):
     """The fused ToMe merge + sequence LayerNorm forward equals the merge kernel followed by
     mmt_seqnorm_fwd bit for bit: merged rows, sizes, position map, y, mean and rstd."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    from tests.seqnorm_ref import expected_rpt
     g = torch.Generator().manual_seed(n * L + t)
     x = (torch.randn((n, L, D), generator=g) * 3 + 1).to(dev)
     metric = torch.randn((n, t, 64), generator=g).bfloat16().to(dev)
@@ -165,6 +166,7 @@ def test_merge_seqnorm_fused_bit_exact(dev, n, L, D, s0, t, r, sized):
     a_y, a_m, a_r = K.seqnorm_fwd(a_x, gamma, beta, 1e-6)
     b_x, b_s, b_p, b_y, b_m, b_r = K.tome_merge_seqnorm_fwd(x, s0, t, r, unm, src, dst, gamma,
                                                             beta, 1e-6, size_in=size)
+    assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_MERGE_SEQ_FWD, expected_rpt(L - r))
     for a, b in ((a_x, b_x), (a_s, b_s), (a_p, b_p), (a_y, b_y), (a_m, b_m), (a_r, b_r)):
         assert torch.equal(a, b)
 
@@ -176,7 +178,8 @@ def test_ln_unmerge_dropout_bwd_fused(dev, n, L, D, s0, t, r, drop):
     """LayerNorm backward + ToMe unmerge + dropout backward in one launch against the three
     kernels in sequence: the unmerged gradient and the dropout output bit for bit, the LayerNorm
     parameter gradients and the bias column sums to fp32 atomic-order rounding."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
+    from tests.seqnorm_ref import expected_rpt
     g = torch.Generator().manual_seed(n * L + r)
     metric = torch.randn((n, t, 64), generator=g).bfloat16().to(dev)
     unm, src, dst = K.tome_match(metric, r)
@@ -196,6 +199,8 @@ def test_ln_unmerge_dropout_bwd_fused(dev, n, L, D, s0, t, r, drop):
     b_g, b_z = K.ln_unmerge_dropout_bwd(dy, x1, mu, rs, gamma, grads[3], grads[4], addend,
                                         (s0, t, r, pos, size, size_out), rng, 3, 1, 0.9, 7 * L,
                                         bias_grad=grads[5])
+    assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_LN_UNMERGE_BWD, expected_rpt(L2),
+                                                 dy_bf16=True)
     assert torch.equal(a_g, b_g)
     assert torch.equal(a_z.view(n, L, D), b_z)
     for i in range(3):
@@ -208,7 +213,7 @@ def test_ln_unmerge_gate_boundary(dev, L2):
     Encoder1DBlock.backward) mirrors the C entry point's limits: at 384 merged rows the fused
     kernel runs and equals the three-kernel path; at 385 the gate says no and the C entry refuses
     (MMTError), so the block takes the three-kernel path instead of failing mid-backward."""
-    from multi_modal_transformers_tokenmerge_amd import _kernels as K
+    from multi_modal_transformers_tokenmerge_amd import _C, _kernels as K
     from multi_modal_transformers_tokenmerge_amd._C import MMTError
     n, D, r, s0 = 2, 64, 16, 32
     L = L2 + r
@@ -229,11 +234,13 @@ def test_ln_unmerge_gate_boundary(dev, L2):
     if K.ln_unmerge_ok(L, L2):
         b_g, b_z = K.ln_unmerge_dropout_bwd(dy, x1, mu, rs, gamma, grads[2], grads[3], None, tome,
                                             None, 3, 1, 1.0, 0)
+        assert _C.norm_last_route() == _C.norm_route(_C.NORM_ROUTE_LN_UNMERGE_BWD, 0, dy_bf16=True)
         assert torch.equal(a_g, b_g) and torch.equal(a_z.view(n, L, D), b_z)
     else:
         with pytest.raises(MMTError):
             K.ln_unmerge_dropout_bwd(dy, x1, mu, rs, gamma, grads[2], grads[3], None, tome, None, 3,
                                      1, 1.0, 0)
+        assert _C.norm_last_route() == _C.NORM_ROUTE_NONE
 
 
 def test_out_of_range_indices_are_reported_not_faulted(dev):
