@@ -546,11 +546,60 @@ int mmt_dropout_bwd(const void* dy, int dtype, int64_t ldy, int M, int N, const 
                     int64_t ldz, float* colsum, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ image tokenizer stem
- * tokenizers/images/image_tokenizer.py: image_to_patches (:35-71, raster "(h p1)(w p2) -> (h w)",
+ * Operand rules of the stem entry points (csrc/stem.hip), checked before anything is launched
+ * (MMT_ERR_INVALID, the message names the entry point). Every tensor is contiguous. A pointer
+ * that its kernels move as vectors or dwords must be aligned to that width, whichever kernel
+ * form the shape selects; every other pointer is read and written one element at a time:
+ *   mmt_patch_im2col        out 16 B (16-B and 8-B stores); img 4 B (dword reads of uint8
+ *                           pixels, fp32 pixels); B, I, Himg, C, P, KH, KW, S > 0, Himg % P == 0,
+ *                           KH, KW <= P, KH*KW*C % 8 == 0, in_dtype 0 or 2
+ *   mmt_stem_conv_pool      img 4 B (dword reads); B, I > 0, Himg >= 16, Himg % 16 == 0
+ *   mmt_stem_conv_wgrad     img 4 B; the same shape rules; slab_elems >= slabs * 64 * 432
+ *   mmt_maxpool_patch       npatch, win, C > 0, win <= 255 (the slot is stored in a byte)
+ *   mmt_maxpool_patch_bwd   dpooled 16 B, argmax 8 B, G 16 B; npatch, win, C > 0, win <= 255,
+ *                           C % 8 == 0
+ *   mmt_maxpool2d, _bwd     npatch, C, KP > 0, KP*KP <= 255, OH, OW >= KP
+ *   mmt_im2col_same         x 16 B, cols 16 B; npatch, H, W, C > 0, C % 8 == 0, KS > 0 and odd
+ *   mmt_col2im_same         npatch, H, W, C > 0, KS > 0 and odd
+ *   mmt_groupnorm_gelu_fwd  x 16 B, y 8 B; B, R, C, G > 0, C divides 256, G divides C
+ *   mmt_groupnorm_gelu_bwd  dy, x, dx 16 B; the same shape rules
+ *   mmt_patch_positions     B, I, P > 0, Himg % P == 0, Q > 1; rng needed in train mode
+ * Nothing outside the stated extents is read or written.
+ *
+ * The kernel form that the last call of a stem entry point launched: MMT_STEM_ROUTE_NONE after a
+ * call rejected before any launch, else the entry point's code, the form MMT_STEM_ROUTE_FORM
+ * (mmt_patch_im2col: MMT_STEM_IM2COL_GENERIC / _ROWS / _LDS; mmt_groupnorm_gelu_fwd / _bwd: 0 for
+ * the general kernel, else the NV = 4 / 8 / 16 / 32 float4 per thread of the register-resident
+ * kernel, taken when R*C == NV*1024 with C a power of two in [4, 256]; 0 for every other entry)
+ * and MMT_STEM_ROUTE_IN_U8 when mmt_patch_im2col read uint8 pixels. mmt_stem_conv_wgrad_slabs
+ * launches nothing and leaves the value alone. Process-wide, not thread-safe. */
+enum {
+  MMT_STEM_ROUTE_NONE = 0,
+  MMT_STEM_ROUTE_PATCH_IM2COL = 1,
+  MMT_STEM_ROUTE_CONV_POOL = 2,
+  MMT_STEM_ROUTE_CONV_WGRAD = 3,
+  MMT_STEM_ROUTE_MAXPOOL_PATCH = 4,
+  MMT_STEM_ROUTE_MAXPOOL_PATCH_BWD = 5,
+  MMT_STEM_ROUTE_GN_GELU_FWD = 6,
+  MMT_STEM_ROUTE_GN_GELU_BWD = 7,
+  MMT_STEM_ROUTE_PATCH_POSITIONS = 8,
+  MMT_STEM_ROUTE_MAXPOOL2D = 9,
+  MMT_STEM_ROUTE_MAXPOOL2D_BWD = 10,
+  MMT_STEM_ROUTE_IM2COL_SAME = 11,
+  MMT_STEM_ROUTE_COL2IM_SAME = 12,
+  MMT_STEM_ROUTE_ENTRY_MASK = 0xff,
+  MMT_STEM_ROUTE_IN_U8 = 0x10000
+};
+enum { MMT_STEM_IM2COL_GENERIC = 0, MMT_STEM_IM2COL_ROWS = 1, MMT_STEM_IM2COL_LDS = 2 };
+#define MMT_STEM_ROUTE_FORM(route) (((route) >> 8) & 0xff)
+int mmt_stem_last_route(void);
+/* tokenizers/images/image_tokenizer.py: image_to_patches (:35-71, raster "(h p1)(w p2) -> (h w)",
  * normalise 2*(x/255)-1) fused with the im2col of the input Conv (KHxKW stride S VALID, Flax HWIO
  * kernel order (ky, kx, c)), :158. img: (B, I, H, H, C) fp32 (in_dtype 0) or uint8 (in_dtype 2);
  * out: bf16 [B*I*NP*OH*OW][KH*KW*C]. H % P != 0 is rejected (the reference's resize branch,
- * :54-59, is broken). */
+ * :54-59, is broken). Forms: KW*C == 36 (the 12x12 RGB stem conv) takes the LDS-staged kernel for
+ * uint8 pixels while 8 patches fit 64 KB of LDS as bf16 (P*C % 4 == 0, P*P*C*16 <= 65536), else
+ * the row-segment kernel; every other shape the generic kernel. */
 int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int Himg, int C, int P, int KH,
                      int KW, int S, int normalize, void* out, mmt_stream_t stream);
 /* max_pool over the `win` conv outputs of each patch (3x3 s1 VALID on the 3x3 map, :159) with

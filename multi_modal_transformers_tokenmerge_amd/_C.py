@@ -46,6 +46,7 @@ SIGNATURES: dict[str, list] = {
     "mmt_gemm_last_route": [],
     "mmt_attn_last_route": [],
     "mmt_norm_last_route": [],
+    "mmt_stem_last_route": [],
     "mmt_set_deterministic": [P, P, L],
     "mmt_det_flush": [P, P, L, P],
     "mmt_gemm_colsum_rows": [I, I, I, I, I, I, I],
@@ -123,6 +124,7 @@ _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: erro
             "mmt_gemm_last_route": I,     # returns a ROUTE_* value
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
             "mmt_norm_last_route": I,     # returns a NORM_ROUTE_* value
+            "mmt_stem_last_route": I,     # returns a STEM_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -242,6 +244,26 @@ def norm_route(entry: int, rpt: int, x_bf16: bool = False, dy_bf16: bool = False
 
 def norm_last_route() -> int:
     return call("mmt_norm_last_route")
+
+
+# MMT_STEM_ROUTE_* (include/mmt_api.h): what mmt_stem_last_route() reports
+(STEM_ROUTE_NONE, STEM_ROUTE_PATCH_IM2COL, STEM_ROUTE_CONV_POOL, STEM_ROUTE_CONV_WGRAD,
+ STEM_ROUTE_MAXPOOL_PATCH, STEM_ROUTE_MAXPOOL_PATCH_BWD, STEM_ROUTE_GN_GELU_FWD,
+ STEM_ROUTE_GN_GELU_BWD, STEM_ROUTE_PATCH_POSITIONS, STEM_ROUTE_MAXPOOL2D, STEM_ROUTE_MAXPOOL2D_BWD,
+ STEM_ROUTE_IM2COL_SAME, STEM_ROUTE_COL2IM_SAME) = range(13)
+STEM_ROUTE_ENTRY_MASK, STEM_ROUTE_IN_U8 = 0xff, 0x10000
+STEM_IM2COL_GENERIC, STEM_IM2COL_ROWS, STEM_IM2COL_LDS = range(3)   # forms of mmt_patch_im2col
+
+
+def stem_route(entry: int, form: int = 0, in_u8: bool = False) -> int:
+    """The route of `entry` in `form` (MMT_STEM_ROUTE_FORM: a STEM_IM2COL_* value for
+    mmt_patch_im2col, the register kernel's NV or 0 for the GroupNorm entries) and, for
+    mmt_patch_im2col, whether the pixels were uint8."""
+    return entry | form << 8 | (STEM_ROUTE_IN_U8 if in_u8 else 0)
+
+
+def stem_last_route() -> int:
+    return call("mmt_stem_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

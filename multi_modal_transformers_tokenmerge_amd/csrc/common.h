@@ -133,6 +133,17 @@ inline bool ln_operand_ok(const void* p, int64_t s_b, int64_t s_t, int D) {
   return ((uintptr_t)p & 15) == 0 && s_b % 8 == 0 && s_t % 8 == 0 && s_t >= D;
 }
 
+// The kernel form of the last image-stem launch (MMT_STEM_ROUTE_*, include/mmt_api.h;
+// mmt_stem_last_route): set by every entry point of stem.hip next to its launch,
+// MMT_STEM_ROUTE_NONE after a call rejected before its launch. Defined in core.hip. Process-wide,
+// not thread-safe.
+extern int g_stem_route;
+inline int stem_route(int entry, int form, bool in_u8) {
+  return entry | form << 8 | (in_u8 ? MMT_STEM_ROUTE_IN_U8 : 0);
+}
+// base pointer of an operand moved as `bytes`-wide vectors (a power of two)
+inline bool aligned_to(const void* p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
 // ---------------------------------------------------------------- wave helpers (wave64)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

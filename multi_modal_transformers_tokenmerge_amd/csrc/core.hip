@@ -33,6 +33,9 @@ extern "C" const char* mmt_last_error(void) { return mmt::g_err; }
 // the kernel form of the last sequence-LN launch (common.h; set by norm.hip and tome.hip)
 int mmt::g_norm_route = MMT_NORM_ROUTE_NONE;
 extern "C" int mmt_norm_last_route(void) { return mmt::g_norm_route; }
+// the kernel form of the last image-stem launch (common.h; set by stem.hip)
+int mmt::g_stem_route = MMT_STEM_ROUTE_NONE;
+extern "C" int mmt_stem_last_route(void) { return mmt::g_stem_route; }
 
 extern "C" int mmt_device_status(mmt_stream_t stream) {
   unsigned int* w = mmt::fault_word();

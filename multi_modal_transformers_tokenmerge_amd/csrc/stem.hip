@@ -536,8 +536,8 @@ __device__ __forceinline__ float gelu_tanh_grad(float z) {
   return 0.5f * (1.f + th) + 0.5f * z * (1.f - th * th) * k0 * (1.f + 3.f * k1 * z * z);
 }
 
-// GroupNorm + gelu forward over x (B, R, C) bf16: one workgroup per sample; stats per group of
-// C/G adjacent channels over all R rows. y = gelu((x - mu) * rstd * gamma + beta).
+// GroupNorm + gelu forward over x (B, R, C) fp32: one workgroup per sample; stats per group of
+// C/G adjacent channels over all R rows. y = gelu((x - mu) * rstd * gamma + beta), stored as bf16.
 constexpr int GN_NT = 256;
 __global__ __launch_bounds__(GN_NT) void groupnorm_gelu_fwd_kernel(
     const float* __restrict__ x, int R, int C, int G, float eps, const float* __restrict__ gamma,
@@ -655,7 +655,7 @@ __global__ __launch_bounds__(GN_NT) void groupnorm_gelu_bwd_kernel(
   }
 }
 
-// Register-resident variants (R*C == NV * GN_NT * 4, C a power of two <= 256): every thread
+// Register-resident variants (R*C == NV * GN_NT * 4, C a power of two in [4, 256]): every thread
 // keeps its NV float4 of the sample in registers, so x (and dy) are read once with all loads in
 // flight, and each thread owns one fixed channel quad c0..c0+3 ((4 t) % C): the per-channel sums
 // reduce across the lanes sharing it with xor shuffles, then across the 4 waves in LDS.
@@ -876,9 +876,11 @@ __global__ void patch_positions_kernel(const uint32_t* __restrict__ rng, uint32_
 extern "C" int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int Himg, int C,
                                 int P, int KH, int KW, int S, int normalize, void* out,
                                 mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(img && out && B > 0 && I > 0 && Himg > 0 && C > 0 && P > 0, "mmt_patch_im2col: args");
   MMT_CHECK_ARG(Himg % P == 0, "mmt_patch_im2col: image %d not divisible by patch %d (the "
                 "reference's resize branch image_tokenizer.py:54-59 is broken; rejected)", Himg, P);
+  MMT_CHECK_ARG(KH > 0 && KW > 0, "mmt_patch_im2col: KH=%d KW=%d must be positive", KH, KW);
   MMT_CHECK_ARG(KH <= P && KW <= P && S > 0, "mmt_patch_im2col: kernel larger than patch");
   const int OH = (P - KH) / S + 1, OW = (P - KW) / S + 1;
   const int K = KH * KW * C;
@@ -889,6 +891,9 @@ extern "C" int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int
   const float sc = normalize ? 1.f : 0.f, bi = 0.f;  // sc: the normalize flag of normalize_px
   const int64_t s_img = (int64_t)Himg * Himg * C;
   MMT_CHECK_ARG(in_dtype == 2 || in_dtype == MMT_F32, "mmt_patch_im2col: dtype must be fp32 (0) or uint8 (2)");
+  MMT_CHECK_ARG(aligned_to(out, 16) && aligned_to(img, 4),
+                "mmt_patch_im2col: out must be 16-B aligned, img 4-B aligned");
+  const bool u8 = in_dtype == 2;
   if (KW * C == 36 && in_dtype == 2 && (P * C) % 4 == 0 && P * P * C * 2 * 8 <= 65536) {
     // the 12x12 RGB stem conv (gato_resnet.yaml:45-60) on uint8 images: LDS-staged kernel
     const int64_t npatch = (int64_t)B * I * NP;
@@ -896,7 +901,8 @@ extern "C" int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int
     hipLaunchKernelGGL((patch_im2col_lds_kernel<36, PG>), dim3((npatch + PG - 1) / PG), dim3(256),
                        (size_t)PG * P * P * C * 2, as_stream(stream), (const uint8_t*)img, s_img,
                        Himg, C, P, KH, S, OH, OW, npatch, K, (bf16_t*)out, sc);
-  } else if (KW * C == 36) {  // row-segment kernel (fp32 images)
+    g_stem_route = stem_route(MMT_STEM_ROUTE_PATCH_IM2COL, MMT_STEM_IM2COL_LDS, true);
+  } else if (KW * C == 36) {  // row-segment kernel (fp32 images, uint8 patches too large for LDS)
     const int64_t nr = rows * KH;
     if (in_dtype == 2)
       hipLaunchKernelGGL((patch_im2col_rows_kernel<uint8_t, 36>), dim3((nr + 255) / 256), dim3(256),
@@ -906,16 +912,18 @@ extern "C" int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int
       hipLaunchKernelGGL((patch_im2col_rows_kernel<float, 36>), dim3((nr + 255) / 256), dim3(256),
                          0, as_stream(stream), (const float*)img, s_img, Himg, C, P, KH, S, OH, OW,
                          rows, K, (bf16_t*)out, sc, bi);
-  } else if (in_dtype == 2)  // uint8
-    hipLaunchKernelGGL(patch_im2col_kernel<uint8_t>, dim3((n + 255) / 256), dim3(256), 0,
-                       as_stream(stream), (const uint8_t*)img, s_img, Himg, C, P, KH, KW, S, OH,
-                       OW, rows, K, (bf16_t*)out, sc, bi);
-  else if (in_dtype == MMT_F32)
-    hipLaunchKernelGGL(patch_im2col_kernel<float>, dim3((n + 255) / 256), dim3(256), 0,
-                       as_stream(stream), (const float*)img, s_img, Himg, C, P, KH, KW, S, OH, OW,
-                       rows, K, (bf16_t*)out, sc, bi);
-  else
-    MMT_CHECK_ARG(false, "mmt_patch_im2col: dtype must be fp32 (0) or uint8 (2)");
+    g_stem_route = stem_route(MMT_STEM_ROUTE_PATCH_IM2COL, MMT_STEM_IM2COL_ROWS, u8);
+  } else {
+    if (u8)
+      hipLaunchKernelGGL(patch_im2col_kernel<uint8_t>, dim3((n + 255) / 256), dim3(256), 0,
+                         as_stream(stream), (const uint8_t*)img, s_img, Himg, C, P, KH, KW, S, OH,
+                         OW, rows, K, (bf16_t*)out, sc, bi);
+    else
+      hipLaunchKernelGGL(patch_im2col_kernel<float>, dim3((n + 255) / 256), dim3(256), 0,
+                         as_stream(stream), (const float*)img, s_img, Himg, C, P, KH, KW, S, OH,
+                         OW, rows, K, (bf16_t*)out, sc, bi);
+    g_stem_route = stem_route(MMT_STEM_ROUTE_PATCH_IM2COL, MMT_STEM_IM2COL_GENERIC, u8);
+  }
   MMT_CHECK_LAUNCH("mmt_patch_im2col");
   return MMT_OK;
 }
@@ -923,14 +931,17 @@ extern "C" int mmt_patch_im2col(const void* img, int in_dtype, int B, int I, int
 extern "C" int mmt_stem_conv_pool(const void* img, int B, int I, int Himg, const void* w,
                                   const float* bias, float* pooled, uint8_t* argmax,
                                   mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(img && w && bias && pooled && argmax && B > 0 && I > 0 && Himg >= 16 &&
                     Himg % 16 == 0, "mmt_stem_conv_pool: args");
+  MMT_CHECK_ARG(aligned_to(img, 4), "mmt_stem_conv_pool: img must be 4-B aligned");
   const int PPD = Himg / 16;
   const int64_t n_tiles = (int64_t)B * I * PPD * ((PPD + 15) / 16);
   const int grid = (int)std::min<int64_t>(n_tiles, 2 * 256);
   hipLaunchKernelGGL(stem_conv_pool_kernel, dim3(grid), dim3(256), 0, as_stream(stream),
                      (const uint8_t*)img, (int64_t)Himg * Himg * 3, Himg, n_tiles,
                      (const bf16_t*)w, bias, pooled, argmax);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_CONV_POOL, 0, false);
   MMT_CHECK_LAUNCH("mmt_stem_conv_pool");
   return MMT_OK;
 }
@@ -946,36 +957,46 @@ extern "C" int mmt_stem_conv_wgrad_slabs(int B, int I, int Himg) {
 extern "C" int mmt_stem_conv_wgrad(const void* img, int B, int I, int Himg, const float* dpooled,
                                    const uint8_t* argmax, float* slab, int64_t slab_elems,
                                    mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   const int grid = mmt_stem_conv_wgrad_slabs(B, I, Himg);
   MMT_CHECK_ARG(img && dpooled && argmax && slab && grid > 0 && slab_elems >= (int64_t)grid * 64 * 432,
                 "mmt_stem_conv_wgrad: args (slab of mmt_stem_conv_wgrad_slabs x 64 x 432 floats)");
+  MMT_CHECK_ARG(aligned_to(img, 4), "mmt_stem_conv_wgrad: img must be 4-B aligned");
   const int PPD = Himg / 16;
   const int64_t n_tiles = (int64_t)B * I * PPD * ((PPD + 15) / 16);
   hipLaunchKernelGGL(stem_conv_wgrad_kernel, dim3(grid), dim3(256), 0, as_stream(stream),
                      (const uint8_t*)img, (int64_t)Himg * Himg * 3, Himg, n_tiles, dpooled, argmax,
                      slab);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_CONV_WGRAD, 0, false);
   MMT_CHECK_LAUNCH("mmt_stem_conv_wgrad");
   return MMT_OK;
 }
 
 extern "C" int mmt_maxpool_patch(const void* conv, int64_t npatch, int win, int C, void* pooled,
                                  uint8_t* argmax, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(conv && pooled && argmax && npatch > 0 && win > 0 && win <= 255 && C > 0,
                 "mmt_maxpool_patch: args");
   const int64_t n = npatch * C;
   hipLaunchKernelGGL(maxpool_patch_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      (const float*)conv, npatch, win, C, (float*)pooled, argmax);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_MAXPOOL_PATCH, 0, false);
   MMT_CHECK_LAUNCH("mmt_maxpool_patch");
   return MMT_OK;
 }
 
 extern "C" int mmt_maxpool_patch_bwd(const void* dpooled, const uint8_t* argmax, int64_t npatch,
                                      int win, int C, void* G, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(dpooled && argmax && G && npatch > 0 && win > 0 && C > 0 && C % 8 == 0,
                 "mmt_maxpool_patch_bwd: args (C %% 8 == 0)");
+  MMT_CHECK_ARG(win <= 255, "mmt_maxpool_patch_bwd: win=%d exceeds the byte slot (255)", win);
+  MMT_CHECK_ARG(aligned_to(dpooled, 16) && aligned_to(argmax, 8) && aligned_to(G, 16),
+                "mmt_maxpool_patch_bwd: dpooled and G must be 16-B aligned, argmax 8-B aligned");
   const int64_t n = npatch * win * (C / 8);
   hipLaunchKernelGGL(maxpool_patch_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0,
                      as_stream(stream), (const float*)dpooled, argmax, npatch, win, C, (bf16_t*)G);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_MAXPOOL_PATCH_BWD, 0, false);
   MMT_CHECK_LAUNCH("mmt_maxpool_patch_bwd");
   return MMT_OK;
 }
@@ -983,9 +1004,12 @@ extern "C" int mmt_maxpool_patch_bwd(const void* dpooled, const uint8_t* argmax,
 extern "C" int mmt_groupnorm_gelu_fwd(const void* x, int B, int R, int C, int G, float eps,
                                       const float* gamma, const float* beta, void* y, float* mean,
                                       float* rstd, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(x && y && gamma && beta && mean && rstd && B > 0 && R > 0,
                 "mmt_groupnorm_gelu_fwd: args");
   MMT_CHECK_ARG(C > 0 && GN_NT % C == 0 && G > 0 && C % G == 0, "mmt_groupnorm_gelu_fwd: C=%d G=%d", C, G);
+  MMT_CHECK_ARG(aligned_to(x, 16) && aligned_to(y, 8),
+                "mmt_groupnorm_gelu_fwd: x must be 16-B aligned, y 8-B aligned");
   const int nv = gn_reg_nv(R, C);
 #define GN_FWD_REG(NV_)                                                                          \
   hipLaunchKernelGGL(groupnorm_gelu_fwd_reg_kernel<NV_>, dim3(B), dim3(GN_NT), 0, as_stream(stream), \
@@ -1000,6 +1024,7 @@ extern "C" int mmt_groupnorm_gelu_fwd(const void* x, int B, int R, int C, int G,
                        (const float*)x, R, C, G, eps, gamma, beta, (bf16_t*)y, mean, rstd);
   }
 #undef GN_FWD_REG
+  g_stem_route = stem_route(MMT_STEM_ROUTE_GN_GELU_FWD, nv, false);
   MMT_CHECK_LAUNCH("mmt_groupnorm_gelu_fwd");
   return MMT_OK;
 }
@@ -1008,9 +1033,12 @@ extern "C" int mmt_groupnorm_gelu_bwd(const void* dy, const void* x, int B, int 
                                       const float* gamma, const float* beta, const float* mean,
                                       const float* rstd, void* dx, int accumulate, float* dgamma,
                                       float* dbeta, mmt_stream_t stream) {
-  MMT_CHECK_ARG(dy && x && dx && gamma && beta && mean && rstd && dgamma && dbeta && B > 0,
+  g_stem_route = MMT_STEM_ROUTE_NONE;
+  MMT_CHECK_ARG(dy && x && dx && gamma && beta && mean && rstd && dgamma && dbeta && B > 0 && R > 0,
                 "mmt_groupnorm_gelu_bwd: args");
   MMT_CHECK_ARG(C > 0 && GN_NT % C == 0 && G > 0 && C % G == 0, "mmt_groupnorm_gelu_bwd: C/G");
+  MMT_CHECK_ARG(aligned_to(dy, 16) && aligned_to(x, 16) && aligned_to(dx, 16),
+                "mmt_groupnorm_gelu_bwd: dy, x and dx must be 16-B aligned");
   const int nv = gn_reg_nv(R, C);
 #define GN_BWD_REG(NV_)                                                                          \
   hipLaunchKernelGGL(groupnorm_gelu_bwd_reg_kernel<NV_>, dim3(B), dim3(GN_NT), 0, as_stream(stream), \
@@ -1027,6 +1055,7 @@ extern "C" int mmt_groupnorm_gelu_bwd(const void* dy, const void* x, int B, int 
                        (float*)dx, accumulate, dgamma, dbeta);
   }
 #undef GN_BWD_REG
+  g_stem_route = stem_route(MMT_STEM_ROUTE_GN_GELU_BWD, nv, false);
   MMT_CHECK_LAUNCH("mmt_groupnorm_gelu_bwd");
   return MMT_OK;
 }
@@ -1034,6 +1063,7 @@ extern "C" int mmt_groupnorm_gelu_bwd(const void* dy, const void* x, int B, int 
 extern "C" int mmt_patch_positions(const uint32_t* rng, uint32_t site, int B, int I, int Himg,
                                    int P, int Q, int train, int64_t sample_offset, int32_t* row_tok,
                                    int32_t* col_tok, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(row_tok && col_tok && B > 0 && I > 0 && P > 0 && Himg % P == 0 && Q > 1,
                 "mmt_patch_positions: args");
   MMT_CHECK_ARG(!train || rng, "mmt_patch_positions: train mode needs the rng state");
@@ -1042,50 +1072,62 @@ extern "C" int mmt_patch_positions(const uint32_t* rng, uint32_t site, int B, in
   hipLaunchKernelGGL(patch_positions_kernel, dim3((n + 255) / 256), dim3(256), 0,
                      as_stream(stream), rng, site, B, I, Himg, P, Q, train, sample_offset, row_tok,
                      col_tok);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_PATCH_POSITIONS, 0, false);
   MMT_CHECK_LAUNCH("mmt_patch_positions");
   return MMT_OK;
 }
 
 extern "C" int mmt_maxpool2d(const void* x, int64_t npatch, int OH, int OW, int C, int KP, void* y,
                              uint8_t* argmax, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(x && y && argmax && npatch > 0 && C > 0 && KP > 0 && KP * KP <= 255 && OH >= KP &&
                     OW >= KP, "mmt_maxpool2d: args");
   const int64_t n = npatch * (OH - KP + 1) * (OW - KP + 1) * C;
   hipLaunchKernelGGL(maxpool2d_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      (const float*)x, npatch, OH, OW, C, KP, (float*)y, argmax);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_MAXPOOL2D, 0, false);
   MMT_CHECK_LAUNCH("mmt_maxpool2d");
   return MMT_OK;
 }
 
 extern "C" int mmt_maxpool2d_bwd(const void* dy, const uint8_t* argmax, int64_t npatch, int OH,
                                  int OW, int C, int KP, void* G, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(dy && argmax && G && npatch > 0 && C > 0 && KP > 0 && OH >= KP && OW >= KP,
                 "mmt_maxpool2d_bwd: args");
+  MMT_CHECK_ARG(KP * KP <= 255, "mmt_maxpool2d_bwd: KP=%d: KP*KP exceeds the byte slot (255)", KP);
   const int64_t n = npatch * OH * OW * C;
   hipLaunchKernelGGL(maxpool2d_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      (const float*)dy, argmax, npatch, OH, OW, C, KP, (bf16_t*)G);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_MAXPOOL2D_BWD, 0, false);
   MMT_CHECK_LAUNCH("mmt_maxpool2d_bwd");
   return MMT_OK;
 }
 
 extern "C" int mmt_im2col_same(const void* x, int64_t npatch, int H, int W, int C, int KS,
                                void* cols, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(x && cols && npatch > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && KS > 0 &&
                     KS % 2 == 1, "mmt_im2col_same: args (C %% 8 == 0, odd KS)");
+  MMT_CHECK_ARG(aligned_to(x, 16) && aligned_to(cols, 16),
+                "mmt_im2col_same: x and cols must be 16-B aligned");
   const int64_t n = npatch * H * W * KS * KS * (C / 8);
   hipLaunchKernelGGL(im2col_same_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      (const bf16_t*)x, npatch, H, W, C, KS, (bf16_t*)cols);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_IM2COL_SAME, 0, false);
   MMT_CHECK_LAUNCH("mmt_im2col_same");
   return MMT_OK;
 }
 
 extern "C" int mmt_col2im_same(const float* dcols, int64_t npatch, int H, int W, int C, int KS,
                                float* dx, mmt_stream_t stream) {
+  g_stem_route = MMT_STEM_ROUTE_NONE;
   MMT_CHECK_ARG(dcols && dx && npatch > 0 && H > 0 && W > 0 && C > 0 && KS > 0 && KS % 2 == 1,
                 "mmt_col2im_same: args");
   const int64_t n = npatch * H * W * C;
   hipLaunchKernelGGL(col2im_same_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream),
                      dcols, npatch, H, W, C, KS, dx);
+  g_stem_route = stem_route(MMT_STEM_ROUTE_COL2IM_SAME, 0, false);
   MMT_CHECK_LAUNCH("mmt_col2im_same");
   return MMT_OK;
 }
