@@ -776,6 +776,55 @@ int mmt_diffusion_sample(const uint32_t* rng, int B, int A, int steps, int64_t s
                          const void* w1, int64_t ld_w1, const void* w2, const float* b2,
                          const float* coef, const float* z_in, int H, float* actions,
                          float* z_out, mmt_stream_t stream);
+/* The step-table sampler: n_steps affine updates with a clip in one launch, for any action width,
+ *   x <- clip(a_k x + b_k eps_hat(x, t_k) + c_k n_k, -clip, +clip),   k = 0 .. n_steps-1,
+ *   eps_hat = W2 relu(W1x x + Q[t_k] + P[b]) + b2,
+ * which covers DDPM with the reference's frozen noise, DDPM with fresh noise per step and DDIM
+ * (eta = 0); the caller builds the table. P, Q (q_rows, H), w1, w2 (A, H) and b2 as for
+ * mmt_diffusion_sample. step_t (n_steps) int32 and step_coef (n_steps, 3) = [a, b, c] fp32 live on
+ * the device; row k uses Q[step_t[k]]. step_t follows "Device-side index checks": a value outside
+ * [0, q_rows) is replaced by 0 and reported as MMT_FAULT_ROW_INDEX, never followed.
+ * Noise: x_0 = z = z_in (B, A), or a draw. Without MMT_SAMPLE_FRESH_NOISE n_k = z (the
+ * reference's quirk); with it n_k = noise_in[k] ((n_steps, B, A)), or a fresh draw. Draws are
+ * Box-Muller on the counter streams: z from key stream_key(seed, step, 0xFFFE, 3), step k's
+ * noise from stream_key(seed, step, 0xFFFE - k / 240, 16 + k % 240) (the key keeps 8 bits of
+ * its site, so the layer word carries the rest of k: a stream of its own for every k up to 1023,
+ * none of them z's or a training stream; for k < 240 this is site 16 + k of layer 0xFFFE), both
+ * at counter g A + a with g = sample_offset + b, so a shifted batch reproduces its draws and, at
+ * A = 8, z is mmt_diffusion_sample's. z_out (B, A) and noise_out (n_steps, B, A) are optional
+ * and return what was used; noise_in / noise_out need the flag.
+ * With MMT_SAMPLE_DRAWS_ONLY nothing is sampled: one small launch writes z_out and, with fresh
+ * noise, noise_out exactly as the full call would (the per-step launch form of the head takes
+ * its draws from it). At least one of the two outputs is needed; only rng, B, A, n_steps,
+ * sample_offset, flags, z_in, noise_in and the two outputs are read or checked.
+ * Supported: A % 8 == 0, 8 <= A <= 64; H % 8 == 0, H <= 1024; 1 <= n_steps <= 1024; q_rows >= 1;
+ * clip > 0; rng or z_in (and, with the flag, rng or noise_in); ld_w1 % 8 == 0, w1 and w2 16-B
+ * aligned. Anything else is MMT_ERR_INVALID before a launch. Graph-capturable, allocates nothing,
+ * no atomics on the data path (one wave owns a sample): bitwise reproducible run to run.
+ * Rounding model: fp32 operands throughout. The bf16 weights are widened exactly; x, the hidden
+ * layer and all sums stay fp32 (the per-step launch form rounds x and the hidden layer to bf16).
+ * Kernel forms, reported by mmt_sampler_last_route() (MMT_SAMPLER_ROUTE_NONE after a call of
+ * either sampler entry rejected before its launch; process-wide, not thread-safe): one wave per
+ * sample with W1x and W2 in LDS (_STEPS_LDS, while 4 H AP + 2048 ceil(H / 64) bytes <= 160 KB,
+ * AP = A or A + 8 when A / 8 is even), else read from global memory each step (_STEPS_STREAM);
+ * _LEGACY_WAVE is mmt_diffusion_sample's register-resident kernel, _STEPS_DRAWS the
+ * MMT_SAMPLE_DRAWS_ONLY launch. */
+enum { MMT_SAMPLE_FRESH_NOISE = 1, MMT_SAMPLE_DRAWS_ONLY = 2 };
+enum {
+  MMT_SAMPLER_ROUTE_NONE = 0,
+  MMT_SAMPLER_ROUTE_LEGACY_WAVE = 1,
+  MMT_SAMPLER_ROUTE_STEPS_LDS = 2,
+  MMT_SAMPLER_ROUTE_STEPS_STREAM = 3,
+  MMT_SAMPLER_ROUTE_STEPS_DRAWS = 4
+};
+int mmt_diffusion_sample_steps(const uint32_t* rng, int B, int A, int n_steps,
+                               int64_t sample_offset, const float* P, int64_t ld_p, const float* Q,
+                               int64_t ld_q, int q_rows, const void* w1, int64_t ld_w1,
+                               const void* w2, const float* b2, const int32_t* step_t,
+                               const float* step_coef, float clip, int flags, const float* z_in,
+                               const float* noise_in, int H, float* actions, float* z_out,
+                               float* noise_out, mmt_stream_t stream);
+int mmt_sampler_last_route(void);
 
 /* Transposed bf16 weight shadows (this build's layout, no reference twin): for each of n
  * matrices, desc[5i..5i+4] = {src_off, dst_off, rows, cols, first_tile} (elements / 64x64 tiles,

@@ -102,6 +102,9 @@ SIGNATURES: dict[str, list] = {
     "mmt_fourier_bwd": [P, I, I, P, P, P, P],
     "mmt_diffusion_loss": [P, L, P, I, I, F, P, P, P],
     "mmt_diffusion_sample": [P, I, I, I, L, P, L, P, L, P, L, P, P, P, P, I, P, P, P],
+    "mmt_diffusion_sample_steps": [P, I, I, I, L, P, L, P, L, I, P, L, P, P, P, P, F, I, P, P, I, P,
+                                   P, P, P],
+    "mmt_sampler_last_route": [],
     "mmt_rows_group_mean_fwd": [P, L, L, I, I, I, P, I, P, P, P],
     "mmt_rows_group_mean_bwd": [P, I, I, I, P, I, P, P, P],
     "mmt_action_head": [I, P, L, I, I, P, P, I, F, F, P, P, P, P],
@@ -125,6 +128,7 @@ _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: erro
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
             "mmt_norm_last_route": I,     # returns a NORM_ROUTE_* value
             "mmt_stem_last_route": I,     # returns a STEM_ROUTE_* value
+            "mmt_sampler_last_route": I,  # returns a SAMPLER_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -264,6 +268,24 @@ def stem_route(entry: int, form: int = 0, in_u8: bool = False) -> int:
 
 def stem_last_route() -> int:
     return call("mmt_stem_last_route")
+
+
+# MMT_SAMPLER_ROUTE_* (include/mmt_api.h): what mmt_sampler_last_route() reports
+(SAMPLER_ROUTE_NONE, SAMPLER_ROUTE_LEGACY_WAVE, SAMPLER_ROUTE_STEPS_LDS,
+ SAMPLER_ROUTE_STEPS_STREAM, SAMPLER_ROUTE_STEPS_DRAWS) = range(5)
+SAMPLE_FRESH_NOISE, SAMPLE_DRAWS_ONLY = 1, 2   # MMT_SAMPLE_* flags
+
+
+def sampler_steps_route(A: int, H: int) -> int:
+    """The form mmt_diffusion_sample_steps takes at action width A and hidden width H: the
+    LDS-resident one while the padded bf16 W1x and W2 rows fit beside the per-wave P + Q rows."""
+    ap = A if (A // 8) % 2 else A + 8
+    fits = 4 * H * ap + 2048 * ((H + 63) // 64) <= 160 * 1024
+    return SAMPLER_ROUTE_STEPS_LDS if fits else SAMPLER_ROUTE_STEPS_STREAM
+
+
+def sampler_last_route() -> int:
+    return call("mmt_sampler_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

@@ -12,6 +12,7 @@ separately. MLPBlocks here run with dropout disabled, as in the reference (they 
 """
 from __future__ import annotations
 
+import dataclasses
 
 import numpy as np
 import torch
@@ -56,6 +57,60 @@ def alpha_hats_of(betas: np.ndarray) -> np.ndarray:
                     dtype=np.float32)
 
 
+@dataclasses.dataclass(frozen=True)
+class SamplerSpec:
+    """How predict_action turns noise into actions. Every kind is a table of affine updates
+    x <- clip(a_k x + b_k eps_hat(x, t_k) + c_k n_k, -clip, clip) (DiffusionActionHead.sampler_table):
+    kind "ddpm": the S ancestral steps t = S-1 .. 0; "ddim": `steps` deterministic (eta = 0) steps
+    spread evenly over S-1 .. 0. noise "frozen": every step reuses the initial sample z as its
+    noise (the reference's scan never splits its keys, diffusion.py:178); "fresh": a new draw per
+    step. final_noise: whether the t = 0 row adds noise (default: True for frozen, as the
+    reference does, False for fresh). The default spec is the reference's sampler."""
+    kind: str = "ddpm"
+    steps: int | None = None
+    noise: str = "frozen"
+    clip: float = 5.0
+    final_noise: bool | None = None
+
+    def __post_init__(self):
+        if self.kind not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler kind must be 'ddpm' or 'ddim', got {self.kind!r}")
+        if self.noise not in ("frozen", "fresh"):
+            raise ValueError(f"sampler noise must be 'frozen' or 'fresh', got {self.noise!r}")
+        if self.steps is not None and (isinstance(self.steps, bool) or int(self.steps) != self.steps
+                                       or self.steps < 1):
+            raise ValueError(f"sampler steps must be a positive integer, got {self.steps!r}")
+        if not (isinstance(self.clip, (int, float)) and self.clip > 0):   # NaN fails too
+            raise ValueError(f"sampler clip must be positive, got {self.clip!r}")
+        if self.kind == "ddim" and (self.noise == "fresh" or self.final_noise):
+            raise ValueError("the DDIM sampler is deterministic (eta = 0): it takes no step noise")
+
+    @property
+    def fresh(self) -> bool:
+        return self.noise == "fresh"
+
+    @property
+    def adds_final_noise(self) -> bool:
+        return (not self.fresh) if self.final_noise is None else bool(self.final_noise)
+
+    def is_reference(self, diffusion_steps: int) -> bool:
+        """The reference's own sampler: what mmt_diffusion_sample runs."""
+        return (self.kind == "ddpm" and self.steps in (None, diffusion_steps) and not self.fresh
+                and float(self.clip) == 5.0 and self.adds_final_noise)
+
+    @classmethod
+    def of(cls, node) -> "SamplerSpec":
+        """A SamplerSpec from None (the default), a spec or a mapping of its fields."""
+        if node is None:
+            return cls()
+        if isinstance(node, cls):
+            return node
+        try:
+            return cls(**dict(node))
+        except TypeError as e:
+            raise ValueError(f"bad sampler spec {node!r}: {e}") from None
+
+
 class DiffusionActionHead(Bindable):
     """Reference :68-209: ``DiffusionActionHead(diffusion_steps, attention_pooling,
     denoising_model, rng_collection="diffusion")`` with the model_configs/action_heads/diffusion.yaml
@@ -73,8 +128,10 @@ class DiffusionActionHead(Bindable):
     (``loss_forward`` / ``*_mean``)."""
 
     def __init__(self, diffusion_steps: int = 32, attention_pooling=None, denoising_model=None,
-                 rng_collection: str = "diffusion", *, readout_pooling: str = "mean"):
+                 rng_collection: str = "diffusion", *, readout_pooling: str = "mean",
+                 sampler=None):
         self.steps = int(diffusion_steps)
+        self.sampler = SamplerSpec.of(sampler)   # predict_action's default (a spec or a dict)
         self.rng_collection = rng_collection
         self.attention_pooling = attention_pooling
         if readout_pooling not in ("mean", "attention"):
@@ -106,7 +163,8 @@ class DiffusionActionHead(Bindable):
     @classmethod
     def create(cls, store: ParamStore, name: str, embedding_dim: int, action_dim: int = 8,
                diffusion_steps: int = 32, time_dim: int | None = None,
-               hidden: int | None = None, num_blocks: int = 1) -> "DiffusionActionHead":
+               hidden: int | None = None, num_blocks: int = 1,
+               sampler=None) -> "DiffusionActionHead":
         """The head from its dimensions, declared in ``store`` (the Octo model's path)."""
         D = embedding_dim
         T = time_dim or D
@@ -117,7 +175,7 @@ class DiffusionActionHead(Bindable):
         dm = {"_target_": _REF_DENOISE, "num_blocks": num_blocks,
               "time_encoder": {"_target_": _REF_FOURIER, "output_dim": T, "mlp_block": mlp(T, T)},
               "mlp_block": mlp(hidden or D, action_dim)}
-        return cls(diffusion_steps, None, dm).bind(store, name, D)
+        return cls(diffusion_steps, None, dm, sampler=sampler).bind(store, name, D)
 
     def _declare(self, store: ParamStore, name: str, embedding_dim: int):
         D = embedding_dim
@@ -202,12 +260,14 @@ class DiffusionActionHead(Bindable):
 
     def predict_action(self, readouts: torch.Tensor, train: bool = True, *, rng=None,
                        sample_offset: int = 0, z: torch.Tensor | None = None,
-                       return_noise: bool = False):
-        """Reference :146-209: the 32-step DDPM sampler from the readouts (B, n, D)."""
+                       return_noise: bool = False, sampler=None,
+                       noise: torch.Tensor | None = None):
+        """Reference :146-209: the sampler from the readouts (B, n, D); by default the reference's
+        32-step DDPM loop, else what `sampler` / `noise` ask for (predict_action_mean)."""
         self._ensure(readouts.device, int(readouts.shape[-1]))
         e = torch.empty((readouts.shape[0], self.D), dtype=torch.bfloat16, device=readouts.device)
         return self.predict_action_mean(self._mean_into(readouts, e), rng, sample_offset, z,
-                                        return_noise)
+                                        return_noise, sampler=sampler, noise=noise)
 
     def consts(self, device):
         if device not in self._dev_consts:
@@ -331,32 +391,139 @@ class DiffusionActionHead(Bindable):
         ht = self.t1.fwd(feats, act=K.ACT_RELU)
         return self.t2.fwd(ht)
 
+    def sampler_table(self, spec=None):
+        """The update table of `spec` (default: the head's): (t int32 (K,), coef fp32 (K, 3)) numpy
+        arrays with x <- clip(a x + b eps_hat(x, t) + c n) per row, built in float64 from the
+        schedule. DDPM: t = S-1 .. 0, a = 1/sqrt(alpha_t), b = -a (1 - alpha_t)/sqrt(1 - abar_t),
+        c = sqrt(beta_t) (0 on the t = 0 row without final noise). DDIM (eta = 0), K steps:
+        t_k = round((S-1)(K-1-k)/(K-1)), a = sqrt(abar_prev/abar_t),
+        b = sqrt(1 - abar_prev) - sqrt(abar_prev (1 - abar_t)/abar_t), c = 0, with abar_prev the
+        next row's abar and 1 after the last."""
+        spec = self.sampler if spec is None else SamplerSpec.of(spec)
+        S = self.steps
+        beta = self.betas_np.astype(np.float64)
+        abar = self.alpha_hats_np.astype(np.float64)
+        if spec.kind == "ddpm":
+            if spec.steps not in (None, S):
+                raise ValueError(f"the DDPM sampler walks all {S} diffusion steps, got steps="
+                                 f"{spec.steps}")
+            t = np.arange(S - 1, -1, -1)
+            alpha = 1.0 - beta[t]
+            a = 1.0 / np.sqrt(alpha)
+            b = -a * (1.0 - alpha) / np.sqrt(1.0 - abar[t])
+            c = np.sqrt(beta[t])
+            if not spec.adds_final_noise:
+                c[t == 0] = 0.0
+        else:
+            n = S if spec.steps is None else int(spec.steps)
+            if not 1 <= n <= S:
+                raise ValueError(f"the DDIM sampler needs 1 <= steps <= {S}, got {n}")
+            k = np.arange(n)
+            t = ((S - 1) * (n - 1 - k) + (n - 1) // 2) // (n - 1) if n > 1 else np.array([S - 1])
+            prev = np.concatenate([abar[t[1:]], [1.0]])
+            a = np.sqrt(prev / abar[t])
+            b = np.sqrt(1.0 - prev) - np.sqrt(prev * (1.0 - abar[t]) / abar[t])
+            c = np.zeros(n)
+        return t.astype(np.int32), np.stack([a, b, c], axis=1).astype(np.float32)
+
+    def _table_dev(self, spec: SamplerSpec, device):
+        key = ("table", spec, device)
+        if key not in self._dev_consts:
+            t, coef = self.sampler_table(spec)
+            self._dev_consts[key] = (torch.from_numpy(t).to(device),
+                                     torch.from_numpy(np.ascontiguousarray(coef)).to(device), t)
+        return self._dev_consts[key]
+
+    def _split_first_dense(self, readout_mean):
+        """concatenate([noisy, time_emb, readout]) . W1^T (OctoDenoise :61) split along the input:
+        P (B, H) = readout part, Q (steps, H) = time-embedding part + b1, both fp32."""
+        A, T = self.A, self.time_dim
+        temb = self.time_embeddings(readout_mean.device)
+        w1 = self.d1.w.bf16
+        Q = K.gemm(temb, w1[:, A:A + T], trans_b=True, bias=self.d1.b.data, out_mode=K.OUT_F32)
+        P = K.gemm(readout_mean, w1[:, A + T:], trans_b=True, out_mode=K.OUT_F32)
+        return P, Q
+
+    def _sample_steps(self, readout_mean, rng, sample_offset, z, noise, spec, want_z=False,
+                      want_noise=False):
+        """mmt_diffusion_sample_steps on spec's table. Returns (actions, z_out or None,
+        noise_out or None)."""
+        B, A, dev = readout_mean.shape[0], self.A, readout_mean.device
+        t_dev, coef_dev, t_np = self._table_dev(spec, dev)
+        n = len(t_np)
+        P, Q = self._split_first_dense(readout_mean)
+        w1 = self.d1.w.bf16
+        actions = torch.empty((B, A), dtype=torch.float32, device=dev)
+        z_out = torch.empty((B, A), dtype=torch.float32, device=dev) if want_z else None
+        n_out = (torch.empty((n, B, A), dtype=torch.float32, device=dev)
+                 if want_noise and spec.fresh else None)
+        _C.call("mmt_diffusion_sample_steps", _C.ptr(rng), B, A, n, sample_offset, _C.ptr(P),
+                P.stride(0), _C.ptr(Q), Q.stride(0), Q.shape[0], _C.ptr(w1), w1.stride(0),
+                _C.ptr(self.d2.w.bf16), _C.ptr(self.d2.b.data), _C.ptr(t_dev), _C.ptr(coef_dev),
+                float(spec.clip), _C.SAMPLE_FRESH_NOISE if spec.fresh else 0, _C.ptr(z),
+                _C.ptr(noise), self.hidden, _C.ptr(actions), _C.ptr(z_out), _C.ptr(n_out),
+                _C.stream_ptr())
+        return actions, z_out, n_out
+
+    def _sample_draws(self, B, device, rng, sample_offset, n_steps, fresh, want_z):
+        """The initial sample z (B, A) (want_z) and, with fresh noise, the step noise
+        (n_steps, B, A) that mmt_diffusion_sample_steps would draw, from its draws-only launch."""
+        A = self.A
+        z_out = torch.empty((B, A), dtype=torch.float32, device=device) if want_z else None
+        n_out = torch.empty((n_steps, B, A), dtype=torch.float32, device=device) if fresh else None
+        _C.call("mmt_diffusion_sample_steps", _C.ptr(rng), B, A, n_steps, sample_offset, None, 0,
+                None, 0, 0, None, 0, None, None, None, None, 0.0,
+                (_C.SAMPLE_FRESH_NOISE if fresh else 0) | _C.SAMPLE_DRAWS_ONLY, None, None,
+                self.hidden, None, _C.ptr(z_out), _C.ptr(n_out), _C.stream_ptr())
+        return z_out, n_out
+
     def predict_action_mean(self, readout_mean: torch.Tensor, rng=None, sample_offset: int = 0,
-                            z: torch.Tensor | None = None, return_noise: bool = False):
-        """Reference :146-209 (the 32-step DDPM loop of jax.lax.scan) on the device.
-        readout_mean: (B, D) bf16 = mean of the readout tokens (:102). The initial sample z is
-        drawn from the counter stream (rng = the (seed, step) device tensor, keyed by the global
-        sample index sample_offset + b) unless injected. Returns actions (B, A) fp32 (and z)."""
+                            z: torch.Tensor | None = None, return_noise: bool = False, *,
+                            sampler=None, noise: torch.Tensor | None = None):
+        """Reference :146-209 (the DDPM loop of jax.lax.scan) on the device, and its variants.
+        readout_mean: (B, D) bf16 = mean of the readout tokens (:102). `sampler` (a SamplerSpec or
+        a dict of its fields; default: the head's) picks the update table; `noise` injects the
+        step noise as fp32 (K, B, A), which implies fresh noise. The initial sample z and the
+        step noise are drawn from the counter streams (rng = the (seed, step) device tensor, keyed
+        by the global sample index sample_offset + b) unless injected. Returns actions (B, A) fp32;
+        with return_noise also z and, when the noise is fresh, the step noise (K, B, A).
+        One launch either way for num_blocks == 1: the reference's sampler at A == 8 runs
+        mmt_diffusion_sample, everything else mmt_diffusion_sample_steps; num_blocks > 1 takes
+        the per-step launch loop."""
         if readout_mean.dim() != 2 or readout_mean.shape[1] != self.D \
                 or readout_mean.dtype != torch.bfloat16 or readout_mean.stride(1) != 1:
             raise ValueError(f"readout_mean must be bf16 (B, {self.D}) with unit inner stride")
-        if self.A != 8:
-            raise ValueError("the reference sampler hard-codes an 8-dim action (diffusion.py:200)")
-        if self.extra:
-            return self._predict_action_loop(readout_mean, rng, sample_offset, z, return_noise)
-        B = readout_mean.shape[0]
-        dev = readout_mean.device
-        if z is not None and (tuple(z.shape) != (B, self.A) or z.dtype != torch.float32
+        spec = self.sampler if sampler is None else SamplerSpec.of(sampler)
+        if noise is not None and not spec.fresh:
+            spec = dataclasses.replace(spec, noise="fresh")   # ValueError for DDIM
+        B, A = readout_mean.shape[0], self.A
+        K_steps = len(self.sampler_table(spec)[0]) if noise is not None else 0
+        if z is not None and (tuple(z.shape) != (B, A) or z.dtype != torch.float32
                               or not z.is_contiguous()):
-            raise ValueError(f"z must be contiguous fp32 ({B}, {self.A})")
-        if z is None and rng is None:
-            raise ValueError("need rng (or an injected initial sample z)")
-        A, T = self.A, self.time_dim
-        temb = self.time_embeddings(dev)
+            raise ValueError(f"z must be contiguous fp32 ({B}, {A})")
+        if noise is not None and (tuple(noise.shape) != (K_steps, B, A)
+                                  or noise.dtype != torch.float32 or not noise.is_contiguous()):
+            raise ValueError(f"noise must be contiguous fp32 ({K_steps}, {B}, {A})")
+        if rng is None and (z is None or (spec.fresh and noise is None)):
+            raise ValueError("need rng (or an injected initial sample z and step noise)")
+        if A % 8 or not 8 <= A <= 64:     # the fused kernels, and the loop form's draws
+            raise ValueError(f"the sampler needs an action width in 8, 16 .. 64, got {A}")
+        if self.extra:
+            return self._predict_action_loop(readout_mean, rng, sample_offset, z, return_noise,
+                                             spec=spec, noise=noise)
+        if self.hidden % 8 or self.hidden > 1024:
+            raise ValueError("the fused sampler needs a hidden width that is a multiple of 8, at "
+                             f"most 1024, got {self.hidden}")
+        if not (spec.is_reference(self.steps) and A == 8 and noise is None):
+            actions, z_out, n_out = self._sample_steps(readout_mean, rng, sample_offset, z, noise,
+                                                       spec, want_z=return_noise,
+                                                       want_noise=return_noise)
+            if not return_noise:
+                return actions
+            return (actions, z_out, n_out) if spec.fresh else (actions, z_out)
+        dev = readout_mean.device
+        P, Q = self._split_first_dense(readout_mean)
         w1 = self.d1.w.bf16
-        # concatenate([noisy, time_emb, readout]) . W1^T (OctoDenoise :61) split along the input
-        Q = K.gemm(temb, w1[:, A:A + T], trans_b=True, bias=self.d1.b.data, out_mode=K.OUT_F32)
-        P = K.gemm(readout_mean, w1[:, A + T:], trans_b=True, out_mode=K.OUT_F32)
         actions = torch.empty((B, A), dtype=torch.float32, device=dev)
         z_out = torch.empty((B, A), dtype=torch.float32, device=dev) if return_noise else None
         _C.call("mmt_diffusion_sample", _C.ptr(rng), B, A, self.steps, sample_offset, _C.ptr(P),
@@ -365,30 +532,30 @@ class DiffusionActionHead(Bindable):
                 _C.ptr(z), self.hidden, _C.ptr(actions), _C.ptr(z_out), _C.stream_ptr())
         return (actions, z_out) if return_noise else actions
 
-    def _predict_action_loop(self, readout_mean, rng, sample_offset, z, return_noise):
-        """predict_action for OctoDenoise num_blocks > 1 (the fused one-launch sampler holds one
-        MLPBlock in registers): the reference's 32-step scan (:146-209) as a loop of
-        predict_denoise_term_mean launches and the clipped update on the device; the initial
-        sample z comes from the fused sampler's own counter-stream draw (a one-step launch), so
-        both paths start from the same z. The noisy sample enters the denoiser as its bf16 GEMM
-        operand (the fused kernel keeps it fp32)."""
-        B, A, dev = readout_mean.shape[0], self.A, readout_mean.device
-        if z is None:
-            z = torch.empty((B, A), dtype=torch.float32, device=dev)
-            T = self.time_dim
-            temb = self.time_embeddings(dev)
-            w1 = self.d1.w.bf16
-            Q = K.gemm(temb, w1[:, A:A + T], trans_b=True, bias=self.d1.b.data, out_mode=K.OUT_F32)
-            P = K.gemm(readout_mean, w1[:, A + T:], trans_b=True, out_mode=K.OUT_F32)
-            scratch = torch.empty((B, A), dtype=torch.float32, device=dev)
-            _C.call("mmt_diffusion_sample", _C.ptr(rng), B, A, 1, sample_offset, _C.ptr(P),
-                    P.stride(0), _C.ptr(Q), Q.stride(0), _C.ptr(w1), w1.stride(0),
-                    _C.ptr(self.d2.w.bf16), _C.ptr(self.d2.b.data), _C.ptr(self.sampler_coef(dev)),
-                    None, self.hidden, _C.ptr(scratch), _C.ptr(z), _C.stream_ptr())
-        coef = self.sampler_coef(dev)
+    def _predict_action_loop(self, readout_mean, rng, sample_offset, z, return_noise, *,
+                             spec: SamplerSpec | None = None, noise=None):
+        """predict_action for OctoDenoise num_blocks > 1 (the fused one-launch samplers hold one
+        MLPBlock): the rows of spec's table (default: the head's sampler) as a loop of
+        predict_denoise_term_mean launches and the clipped update on the device. What is not
+        injected of the initial sample z and the step noise comes from the fused entry's own
+        counter-stream draws (its draws-only launch), so both forms consume identical draws. The
+        noisy sample enters the denoiser as its bf16 GEMM operand (the fused kernels keep it
+        fp32)."""
+        spec = self.sampler if spec is None else spec
+        t_dev, coef, t_np = self._table_dev(spec, readout_mean.device)
+        need_noise = spec.fresh and noise is None
+        if z is None or need_noise:
+            z_d, n_d = self._sample_draws(readout_mean.shape[0], readout_mean.device, rng,
+                                          sample_offset, len(t_np), need_noise, z is None)
+            z = z_d if z is None else z
+            noise = n_d if need_noise else noise
         x = z.clone()
-        for t in range(self.steps - 1, -1, -1):
-            tt = torch.full((B,), t, dtype=torch.int32, device=dev)
+        for k, t in enumerate(t_np):
+            tt = torch.full((x.shape[0],), int(t), dtype=torch.int32, device=x.device)
             eps = self.predict_denoise_term_mean(readout_mean, tt, x)
-            x = torch.clamp(coef[t, 0] * (x - coef[t, 1] * eps) + coef[t, 2] * z, -5.0, 5.0)
-        return (x, z) if return_noise else x
+            n = noise[k] if spec.fresh else z
+            x = torch.clamp(coef[k, 0] * x + coef[k, 1] * eps + coef[k, 2] * n,
+                            -float(spec.clip), float(spec.clip))
+        if not return_noise:
+            return x
+        return (x, z, noise) if spec.fresh else (x, z)

@@ -18,7 +18,10 @@ which are not available on the GPU box.
   ``token_compression_method`` ("tome" | "prune"), ``proportional_attention`` (ToMe's log-size
   key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``readout_pooling`` ("mean" |
   "attention": MultiHeadAttentionPooling of the readouts in the diffusion head, with
-  ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node), ``fp8_matmul``, ``t5_num_layers`` and ``text_tokens``.
+  ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node),
+  ``action_heads.action_horizon`` (the diffusion head denoises a chunk of that many actions) and
+  ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``fp8_matmul``,
+  ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
 ``KeyError`` / ``ValueError`` (Hydra raises on both).
@@ -291,6 +294,9 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     if axes is not None:
         kw["pooling_norm_axes"] = tuple(int(v) for v in (axes if isinstance(axes, (list, tuple))
                                                          else [axes]))
+    kw["action_horizon"] = int(heads_cfg.get("action_horizon", 1))
+    sampler = heads_cfg.get("sampler")
+    kw["sampler"] = None if sampler is None else dict(sampler)
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

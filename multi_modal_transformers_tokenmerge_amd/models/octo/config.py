@@ -76,8 +76,23 @@ class OctoConfig:
     pooling_heads: Optional[int] = None
     pooling_mlp_dim: Optional[int] = None
     pooling_norm_axes: tuple = (-1,)
+    # action chunking (Octo / Diffusion Policy): the diffusion head denoises action_horizon
+    # consecutive actions at once, so its width is action_space_dim * action_horizon (YAML key
+    # action_heads.action_horizon). The continuous and categorical heads predict one action.
+    action_horizon: int = 1
+    # the diffusion head's default sampler: the fields of action_heads.diffusion.SamplerSpec as a
+    # dict (YAML key action_heads.sampler), None = the reference's 32-step loop
+    sampler: Optional[dict] = None
 
     def __post_init__(self):
+        if self.action_horizon < 1:
+            raise ValueError(f"action_horizon must be >= 1, got {self.action_horizon}")
+        if self.action_horizon > 1 and set(self.action_heads) - {"diffusion"}:
+            raise ValueError("action_horizon > 1 is the diffusion head's: the continuous and "
+                             f"categorical heads predict one action, got heads {self.action_heads}")
+        if self.sampler is not None:
+            from ...action_heads.diffusion import SamplerSpec
+            SamplerSpec.of(self.sampler)     # ValueError on a bad spec
         if self.readout_pooling not in ("mean", "attention"):
             raise ValueError(f"readout_pooling must be 'mean' or 'attention', got "
                              f"{self.readout_pooling!r}")

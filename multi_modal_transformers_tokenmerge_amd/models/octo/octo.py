@@ -102,8 +102,9 @@ class Octo:
                                                   fp8=cfg.fp8, fp8_residual=cfg.fp8_residual)
         # ---- head
         self.head = DiffusionActionHead.create(store, "diffusion_action_head", D,
-                                               cfg.action_space_dim, cfg.diffusion_steps,
-                                               num_blocks=cfg.denoise_blocks)
+                                               cfg.action_space_dim * cfg.action_horizon,
+                                               cfg.diffusion_steps,
+                                               num_blocks=cfg.denoise_blocks, sampler=cfg.sampler)
         self.continuous_head = self.categorical_head = None
         if "continuous" in cfg.action_heads:
             self.continuous_head = ContinuousActionHead(store, "continuous_action_head", D,
@@ -288,6 +289,7 @@ class Octo:
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
         output for text_tokens computed ahead (generate_readouts)."""
         inject = inject or {}
+        actions = self._chunk_flat(actions)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         inject.get("positions"), inject.get("tome"), t5_out)
         B = xL.shape[0]
@@ -306,6 +308,21 @@ class Octo:
         st.update(head_sv=hsv, xL_shape=tuple(xL.shape), xL=xL)
         return loss, st
 
+    def _chunk_flat(self, actions):
+        """The diffusion head's view of an action chunk: (B, action_horizon, action_space_dim) or
+        the already flat (B, action_horizon * action_space_dim), as (B, h a). A flat tensor is
+        returned as it is."""
+        h, a = self.cfg.action_horizon, self.cfg.action_space_dim
+        if actions.dim() == 3:
+            if tuple(actions.shape[1:]) != (h, a):
+                raise ValueError(f"actions must be (B, {h}, {a}) or (B, {h * a}), got "
+                                 f"{tuple(actions.shape)}")
+            return actions.reshape(actions.shape[0], h * a)
+        if actions.dim() != 2 or actions.shape[1] != h * a:
+            raise ValueError(f"actions must be (B, {h}, {a}) or (B, {h * a}), got "
+                             f"{tuple(actions.shape)}")
+        return actions
+
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
                                        sample_offset=0, train=True):
         """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
@@ -315,10 +332,13 @@ class Octo:
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
-                                 positions=None):
+                                 positions=None, sampler=None):
         """Reference :147-154: readouts (the reference's backbone always runs with
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
-        the 32-step DDPM sampler (action_heads/diffusion.py:146-209). Returns (B, 8) fp32."""
+        the sampler (action_heads/diffusion.py:146-209): `sampler` (a SamplerSpec or a dict of its
+        fields), else OctoConfig.sampler, else the reference's 32-step DDPM loop. Returns fp32
+        (B, action_space_dim), or (B, action_horizon, action_space_dim) with a horizon > 1 (z
+        and the returned noise stay flat, (B, h a))."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions)
         if self.pooling is not None:
             e = self._readout_pooled(xL)
@@ -328,7 +348,12 @@ class Octo:
             _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
                     _C.ptr(self.readout_rows), self.readout_rows.numel(), _C.ptr(e), e.stride(0),
                     _C.stream_ptr())
-        return self.head.predict_action_mean(e, rng, sample_offset, z, return_noise)
+        out = self.head.predict_action_mean(e, rng, sample_offset, z, return_noise, sampler=sampler)
+        h = self.cfg.action_horizon
+        if h == 1:
+            return out
+        chunk = lambda a: a.view(a.shape[0], h, self.cfg.action_space_dim)
+        return (chunk(out[0]), *out[1:]) if return_noise else chunk(out)
 
     def _readout_pooled(self, xL):
         """The diffusion head's conditioning vector (B, D) bf16: the readout mean, or the
