@@ -826,6 +826,60 @@ int mmt_diffusion_sample_steps(const uint32_t* rng, int B, int A, int n_steps,
                                float* noise_out, mmt_stream_t stream);
 int mmt_sampler_last_route(void);
 
+/* The multi-draw diffusion loss: denoise_loss (diffusion.py:110-143) with K independent (t, eps)
+ * draws per sample against one P = readout . W1r^T, and a pad mask over the action components.
+ * P, Q (steps, H), w1, w2 (A, H), b2 as for mmt_diffusion_sample_steps. Per sample b and draw k
+ *   t = t_in[k, b] or U{0..steps-1};  eps = eps_in[k, b] or N(0, 1) (Box-Muller)
+ *   noisy = sqrt(abar_t) a_b + sqrt(1 - abar_t) eps,  abar = alpha_hats (steps)
+ *   pre = W1x noisy + Q[t] + P[b];  h = relu(pre);  pred = W2 h + b2;  d = pred - eps
+ *   loss  = A / (K max(sum m, 1)) sum_{k,b,j} m[b,j] 0.5 d[k,b,j]^2
+ *   dpred = grad_scale A / (K max(sum m, 1)) m d;  dh = (W2^T dpred) [pre > 0];  dP[b] = sum_k dh
+ * m = pad_mask (B, A) uint8 (non-zero: the component counts), NULL = all ones, for which the loss
+ * is the reference's mean_b sum_j 0.5 d^2 averaged over the draws. sum m is counted on the device
+ * by a small launch of this entry; sum m == 0 gives loss 0 and zero gradients.
+ * Outputs: loss[0] (overwritten), t_out (K, B) int32, eps_out (K, B, A) fp32 (optional), and the
+ * five backward operands, bf16, rows k B + b: noisy (K B, A), h (K B, H), dh (K B, H), dpred
+ * (K B, A), and dP (B, H). All five NULL: forward only (evaluation); otherwise all five are given.
+ * scratch: B + 1 fp32 words of the caller (the mask count, then the per-sample loss partials).
+ * An injected t outside [0, steps) follows "Device-side index checks": replaced by 0 (t_out holds
+ * the 0) and reported as MMT_FAULT_ROW_INDEX, never followed.
+ * Draws: draw 0 uses mmt_diffusion_prep's keys (t: stream_key(seed, step, 0xFFFE, 1) at counter
+ * g = sample_offset + b; eps: site 2 at counter g A + j), so K = 1 reproduces its draws bit for
+ * bit. Draw k >= 1 uses layer word 0xFFF9 (no other stream does: 0xFFFA .. 0xFFFE are the head's
+ * and the sampler's, 0xFFFF the stem's), site 2 k for t and 2 k + 1 for eps, same counters.
+ * Supported: A % 8 == 0, 8 <= A <= 64; H % 8 == 0, H <= 1024; 1 <= K <= 64; steps >= 1;
+ * ld_w1 % 8 == 0, w1 and w2 16-B aligned; rng or both injections. Anything else is
+ * MMT_ERR_INVALID before a launch. Graph-capturable, allocates nothing, no float atomics: a wave
+ * owns a sample, the per-sample loss partials are added in ascending order by a last small
+ * launch, and two calls on the same inputs agree bit for bit.
+ * Rounding model: all forward arithmetic is fp32 on exactly widened bf16 weights (as the
+ * sampler); the only bf16 roundings are the five backward outputs, dP being accumulated in fp32
+ * from the unrounded dh and rounded once.
+ * Kernel forms, reported by mmt_diffusion_loss_last_route() (_NONE after a call rejected before
+ * its launch; process-wide, not thread-safe): W1x and W2 in LDS (_LDS, while
+ * 4 H AP + 2048 ceil(H / 64) bytes <= 160 KB, AP = A or A + 8 when A / 8 is even), else read from
+ * global memory each draw (_STREAM). */
+enum {
+  MMT_DIFFUSION_LOSS_ROUTE_NONE = 0,
+  MMT_DIFFUSION_LOSS_ROUTE_LDS = 1,
+  MMT_DIFFUSION_LOSS_ROUTE_STREAM = 2
+};
+int mmt_diffusion_loss_multi(const uint32_t* rng, int B, int A, int K, int steps, int H,
+                             int64_t sample_offset, const float* actions, const uint8_t* pad_mask,
+                             const float* alpha_hats, const float* P, int64_t ld_p, const float* Q,
+                             int64_t ld_q, const void* w1, int64_t ld_w1, const void* w2,
+                             const float* b2, const int32_t* t_in, const float* eps_in,
+                             float grad_scale, float* scratch, float* loss, int32_t* t_out,
+                             float* eps_out, void* noisy, void* h, void* dh, void* dpred, void* dP,
+                             mmt_stream_t stream);
+int mmt_diffusion_loss_last_route(void);
+/* dQ (steps, H) fp32, row stride ld_dq: dQ[t] = sum of the rows r of dh (rows, H) bf16 (row stride
+ * ld_dh) with t_rows[r] == t, added in ascending r (one workgroup per (t, 64 columns), no
+ * atomics: bitwise reproducible); a t no row has gives a zero row. t_rows is mmt_diffusion_loss_multi's
+ * t_out (rows = K B). */
+int mmt_diffusion_loss_dq(const int32_t* t_rows, const void* dh, int64_t ld_dh, int rows, int steps,
+                          int H, float* dQ, int64_t ld_dq, mmt_stream_t stream);
+
 /* Transposed bf16 weight shadows (this build's layout, no reference twin): for each of n
  * matrices, desc[5i..5i+4] = {src_off, dst_off, rows, cols, first_tile} (elements / 64x64 tiles,
  * first_tile = running tile count), dst[dst_off + c*rows + r] = src[src_off + r*cols + c]. */

@@ -105,6 +105,10 @@ SIGNATURES: dict[str, list] = {
     "mmt_diffusion_sample_steps": [P, I, I, I, L, P, L, P, L, I, P, L, P, P, P, P, F, I, P, P, I, P,
                                    P, P, P],
     "mmt_sampler_last_route": [],
+    "mmt_diffusion_loss_multi": [P, I, I, I, I, I, L, P, P, P, P, L, P, L, P, L, P, P, P, P, F, P, P,
+                                 P, P, P, P, P, P, P, P],
+    "mmt_diffusion_loss_last_route": [],
+    "mmt_diffusion_loss_dq": [P, P, L, I, I, I, P, L, P],
     "mmt_rows_group_mean_fwd": [P, L, L, I, I, I, P, I, P, P, P],
     "mmt_rows_group_mean_bwd": [P, I, I, I, P, I, P, P, P],
     "mmt_action_head": [I, P, L, I, I, P, P, I, F, F, P, P, P, P],
@@ -129,6 +133,7 @@ _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: erro
             "mmt_norm_last_route": I,     # returns a NORM_ROUTE_* value
             "mmt_stem_last_route": I,     # returns a STEM_ROUTE_* value
             "mmt_sampler_last_route": I,  # returns a SAMPLER_ROUTE_* value
+            "mmt_diffusion_loss_last_route": I,  # returns a DIFFUSION_LOSS_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
 
 
@@ -286,6 +291,21 @@ def sampler_steps_route(A: int, H: int) -> int:
 
 def sampler_last_route() -> int:
     return call("mmt_sampler_last_route")
+
+
+# MMT_DIFFUSION_LOSS_ROUTE_* (include/mmt_api.h): what mmt_diffusion_loss_last_route() reports
+DIFFUSION_LOSS_ROUTE_NONE, DIFFUSION_LOSS_ROUTE_LDS, DIFFUSION_LOSS_ROUTE_STREAM = range(3)
+
+
+def diffusion_loss_route(A: int, H: int) -> int:
+    """The form mmt_diffusion_loss_multi takes at action width A and hidden width H (the
+    sampler's LDS budget)."""
+    lds = sampler_steps_route(A, H) == SAMPLER_ROUTE_STEPS_LDS
+    return DIFFUSION_LOSS_ROUTE_LDS if lds else DIFFUSION_LOSS_ROUTE_STREAM
+
+
+def diffusion_loss_last_route() -> int:
+    return call("mmt_diffusion_loss_last_route")
 
 
 def workspace_size(op: int, *dims: int) -> int:

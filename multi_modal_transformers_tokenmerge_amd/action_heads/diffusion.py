@@ -9,6 +9,12 @@ output into that same buffer (GEMM with a column-offset output), the readout mea
 its last columns, so ``concatenate([noisy, time_emb, readout])`` (:61) never materialises
 separately. MLPBlocks here run with dropout disabled, as in the reference (they are called without
 ``train``, attention.py:29 default False).
+
+With ``n_diffusion_samples`` > 1 or a pad mask the loss takes another route (``loss_forward_multi``):
+the first Dense is split along its input as in the sampler, the time encoder runs once per
+diffusion step and the readout product once per sample, and one fused kernel
+(``mmt_diffusion_loss_multi``) handles all K draws of a sample; the backward is the split Dense's
+(``_loss_backward_multi``).
 """
 from __future__ import annotations
 
@@ -18,10 +24,11 @@ import numpy as np
 import torch
 
 from .. import _C, _kernels as K
-from ..layers import Dense
+from ..layers import Dense, split_k_for
 from ..module_api import Bindable, init_from_spec, sget, spec
 from ..params import ParamStore
 
+K_ = K   # the kernels module where a method's K is the number of diffusion draws
 _REF = "multi_modal_transformers."
 _REF_MLP = _REF + "attention_blocks.attention.MLPBlock"
 _REF_DENOISE = _REF + "action_heads.diffusion.OctoDenoise"
@@ -129,8 +136,13 @@ class DiffusionActionHead(Bindable):
 
     def __init__(self, diffusion_steps: int = 32, attention_pooling=None, denoising_model=None,
                  rng_collection: str = "diffusion", *, readout_pooling: str = "mean",
-                 sampler=None):
+                 sampler=None, n_diffusion_samples: int = 1):
         self.steps = int(diffusion_steps)
+        if isinstance(n_diffusion_samples, bool) or int(n_diffusion_samples) != n_diffusion_samples \
+                or not 1 <= n_diffusion_samples <= 64:
+            raise ValueError("n_diffusion_samples must be an integer in 1 .. 64, got "
+                             f"{n_diffusion_samples!r}")
+        self.n_diffusion_samples = int(n_diffusion_samples)   # (t, eps) draws per sample in the loss
         self.sampler = SamplerSpec.of(sampler)   # predict_action's default (a spec or a dict)
         self.rng_collection = rng_collection
         self.attention_pooling = attention_pooling
@@ -164,7 +176,7 @@ class DiffusionActionHead(Bindable):
     def create(cls, store: ParamStore, name: str, embedding_dim: int, action_dim: int = 8,
                diffusion_steps: int = 32, time_dim: int | None = None,
                hidden: int | None = None, num_blocks: int = 1,
-               sampler=None) -> "DiffusionActionHead":
+               sampler=None, n_diffusion_samples: int = 1) -> "DiffusionActionHead":
         """The head from its dimensions, declared in ``store`` (the Octo model's path)."""
         D = embedding_dim
         T = time_dim or D
@@ -175,7 +187,8 @@ class DiffusionActionHead(Bindable):
         dm = {"_target_": _REF_DENOISE, "num_blocks": num_blocks,
               "time_encoder": {"_target_": _REF_FOURIER, "output_dim": T, "mlp_block": mlp(T, T)},
               "mlp_block": mlp(hidden or D, action_dim)}
-        return cls(diffusion_steps, None, dm, sampler=sampler).bind(store, name, D)
+        return cls(diffusion_steps, None, dm, sampler=sampler,
+                   n_diffusion_samples=n_diffusion_samples).bind(store, name, D)
 
     def _declare(self, store: ParamStore, name: str, embedding_dim: int):
         D = embedding_dim
@@ -205,6 +218,8 @@ class DiffusionActionHead(Bindable):
                       for i in range(1, self.num_blocks)]
         if self.extra and self.A % 8:
             raise ValueError("OctoDenoise num_blocks > 1 needs action_dim % 8 == 0 (16-B rows)")
+        if self.n_diffusion_samples > 1:
+            self._check_multi(self.n_diffusion_samples)
         if self.pooling is not None and not self.pooling.bound:
             # after the denoiser: the offsets of everything above do not depend on the option (the
             # Octo model binds its module itself, after every head: attach_pooling)
@@ -235,16 +250,25 @@ class DiffusionActionHead(Bindable):
         return out
 
     def denoise_loss(self, readouts: torch.Tensor, actions: torch.Tensor, train: bool = True, *,
-                     rng=None, sample_offset: int = 0) -> torch.Tensor:
+                     rng=None, sample_offset: int = 0, pad_mask=None) -> torch.Tensor:
         """Reference :110-143: t ~ U{0..steps-1}, eps ~ N(0, 1) from the 'diffusion' counter
         stream (rng, keyed by the global sample index), noisy = sqrt(abar) a + sqrt(1 - abar) eps,
-        loss = mean_b sum_a 0.5 (pred - eps)^2. Returns the loss (1,) fp32 on the device."""
+        loss = mean_b sum_a 0.5 (pred - eps)^2. Returns the loss (1,) fp32 on the device.
+        With n_diffusion_samples > 1 the loss averages that many independent (t, eps) draws per
+        sample, and with pad_mask (B, A) bool only its components enter it, normalised by their
+        number (loss_forward_multi); without either, the single-draw launches run unchanged."""
         self._ensure(readouts.device, int(readouts.shape[-1]))
         if rng is None:
             raise ValueError("denoise_loss needs the diffusion rng (rng=)")
         B = readouts.shape[0]
         if tuple(actions.shape) != (B, self.A):
             raise ValueError(f"actions must be ({B}, {self.A})")
+        if self.n_diffusion_samples > 1 or pad_mask is not None:
+            self._check_multi(self.n_diffusion_samples)
+            e = torch.empty((B, self.D), dtype=torch.bfloat16, device=readouts.device)
+            return self.loss_forward_multi(self._mean_into(readouts, e), actions.float().contiguous(),
+                                           rng, sample_offset, self.n_diffusion_samples, pad_mask,
+                                           backward=False)[0]
         cat = self.new_cat(B, readouts.device)
         self._mean_into(readouts, self.readout_slot(cat))
         loss, _ = self.loss_forward(cat, actions.float().contiguous(), rng, sample_offset)
@@ -317,8 +341,104 @@ class DiffusionActionHead(Bindable):
             chain.append((x, h))
         return pred, chain
 
+    # ------------------------------------------------------- multi-draw / masked denoise_loss
+    def _check_multi(self, K: int = 1):
+        """The fused loss (mmt_diffusion_loss_multi) holds one MLPBlock at the fused sampler's
+        widths."""
+        if isinstance(K, bool) or int(K) != K or not 1 <= K <= 64:
+            raise ValueError(f"n_diffusion_samples must be an integer in 1 .. 64, got {K!r}")
+        if self.extra:
+            raise ValueError("n_diffusion_samples > 1 and pad_mask need OctoDenoise num_blocks == 1 "
+                             "(the fused loss holds one MLPBlock, as the fused sampler does)")
+        if self.A % 8 or not 8 <= self.A <= 64:
+            raise ValueError(f"the fused loss needs an action width in 8, 16 .. 64, got {self.A}")
+        if self.hidden % 8 or self.hidden > 1024:
+            raise ValueError("the fused loss needs a hidden width that is a multiple of 8, at "
+                             f"most 1024, got {self.hidden}")
+
+    def loss_forward_multi(self, e: torch.Tensor, actions: torch.Tensor, rng, sample_offset: int = 0,
+                           K: int = 1, pad_mask=None, t_in=None, eps_in=None, backward: bool = True):
+        """denoise_loss (:110-143) with K independent (t, eps) draws per sample against one pooled
+        readout e (B, D) bf16, and a pad mask (B, A) (bool / uint8: components that count). The
+        first Dense is split as in the sampler (_split_first_dense): the time encoder runs once
+        per diffusion step and the readout product once per sample whatever K is; one fused kernel
+        (mmt_diffusion_loss_multi) draws, noises, runs the MLPBlock in fp32 and emits the loss and
+        the backward's bf16 operands. t_in (K, B) int32 / eps_in (K, B, A) fp32 inject the draws.
+        backward=False: forward only (evaluation). Returns (loss (1,) fp32, saved)."""
+        self._check_multi(K)
+        B, A, H, S, dev = e.shape[0], self.A, self.hidden, self.steps, e.device
+        if e.dim() != 2 or e.shape[1] != self.D or e.dtype != torch.bfloat16 or e.stride(1) != 1:
+            raise ValueError(f"the pooled readout must be bf16 (B, {self.D}) with unit inner stride")
+        if tuple(actions.shape) != (B, A) or actions.dtype != torch.float32 \
+                or not actions.is_contiguous():
+            raise ValueError(f"actions must be contiguous fp32 ({B}, {A})")
+        if pad_mask is not None:
+            if tuple(pad_mask.shape) != (B, A) or pad_mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"pad_mask must be bool or uint8 ({B}, {A})")
+            pad_mask = pad_mask.to(torch.uint8).contiguous()
+        if (t_in is None) != (eps_in is None):
+            raise ValueError("inject t and eps together")
+        if t_in is not None:
+            if tuple(t_in.shape) != (K, B) or t_in.dtype != torch.int32 or not t_in.is_contiguous():
+                raise ValueError(f"injected t must be contiguous int32 ({K}, {B})")
+            if tuple(eps_in.shape) != (K, B, A) or eps_in.dtype != torch.float32 \
+                    or not eps_in.is_contiguous():
+                raise ValueError(f"injected eps must be contiguous fp32 ({K}, {B}, {A})")
+        elif rng is None:
+            raise ValueError("need the diffusion rng (or injected t and eps)")
+        temb, feats, ht, t_all = self._time_embeddings_saved(dev)
+        w1 = self.d1.w.bf16
+        Q = K_.gemm(temb, w1[:, A:A + self.time_dim], trans_b=True, bias=self.d1.b.data,
+                    out_mode=K_.OUT_F32)
+        P = K_.gemm(e, w1[:, A + self.time_dim:], trans_b=True, out_mode=K_.OUT_F32)
+        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev) if backward else None
+        t = torch.empty((K, B), dtype=torch.int32, device=dev)
+        eps = torch.empty((K, B, A), dtype=torch.float32, device=dev)
+        noisy, h, dh, dpred, dP = bf(K * B, A), bf(K * B, H), bf(K * B, H), bf(K * B, A), bf(B, H)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        scratch = torch.empty(B + 1, dtype=torch.float32, device=dev)
+        _C.call("mmt_diffusion_loss_multi", _C.ptr(rng), B, A, K, S, H, sample_offset,
+                _C.ptr(actions), _C.ptr(pad_mask), _C.ptr(self.consts(dev)), _C.ptr(P), P.stride(0),
+                _C.ptr(Q), Q.stride(0), _C.ptr(w1), w1.stride(0), _C.ptr(self.d2.w.bf16),
+                _C.ptr(self.d2.b.data), _C.ptr(t_in), _C.ptr(eps_in), 1.0, _C.ptr(scratch),
+                _C.ptr(loss), _C.ptr(t), _C.ptr(eps), _C.ptr(noisy), _C.ptr(h), _C.ptr(dh),
+                _C.ptr(dpred), _C.ptr(dP), _C.stream_ptr())
+        return loss, dict(multi=True, e=e, temb=temb, feats=feats, ht=ht, t_all=t_all, t=t, eps=eps,
+                          noisy=noisy, h=h, dh=dh, dpred=dpred, dP=dP, pad_mask=pad_mask)
+
+    def _loss_backward_multi(self, sv: dict) -> torch.Tensor:
+        """The split-Dense backward of loss_forward_multi, on the GEMM and column-sum paths into
+        the flat gradient buffer. Returns d(pooled readout) (B, D) bf16."""
+        if sv["dP"] is None:
+            raise ValueError("loss_forward_multi ran forward-only (backward=False)")
+        A, T, H, S = self.A, self.time_dim, self.hidden, self.steps
+        dev = sv["dP"].device
+        dh, dP = sv["dh"], sv["dP"]
+        self.d2.bwd(sv["dpred"], sv["h"], need_dx=False)      # dW2 += dpred^T h, db2 += colsum
+        w1g, w1t = self.d1.w.grad, self.d1.w.bf16_t           # (H, A+T+D) fp32, (A+T+D, H) bf16
+        def wgrad(dy, x, cols):   # dW1[:, cols] += dy^T x, as Dense.bwd's weight gradient
+            K_.gemm(dy, x, trans_a=True, out=w1g[:, cols], out_mode=K_.OUT_F32_ACCUM,
+                    split_k=split_k_for(H, x.shape[1], dy.shape[0]))
+        wgrad(dh, sv["noisy"], slice(0, A))                   # dW1[:, :A] += dh^T noisy
+        wgrad(dP, sv["e"], slice(A + T, None))                # dW1[:, A+T:] += dP^T e
+        de = K_.gemm(dP, w1t[A + T:], trans_b=True)           # dP . W1[:, A+T:]
+        dQ = torch.empty((S, H), dtype=torch.float32, device=dev)
+        _C.call("mmt_diffusion_loss_dq", _C.ptr(sv["t"]), _C.ptr(dh), dh.stride(0), dh.shape[0], S,
+                H, _C.ptr(dQ), dQ.stride(0), _C.stream_ptr())
+        K_.colsum(dQ, self.d1.b.grad)                         # db1 += colsum(dQ)
+        dQb = K_.cast_f32_bf16(dQ, torch.empty((S, H), dtype=torch.bfloat16, device=dev))
+        wgrad(dQb, sv["temb"], slice(A, A + T))               # dW1[:, A:A+T] += dQ^T temb
+        dtemb = K_.gemm(dQb, w1t[A:A + T], trans_b=True)      # (steps, T)
+        dzt = self.t2.bwd(dtemb, sv["ht"], gate=sv["ht"], gate_scale=1.0)
+        dfeats = self.t1.bwd(dzt, sv["feats"])
+        _C.call("mmt_fourier_bwd", _C.ptr(dfeats), S, self.F, _C.ptr(sv["t_all"]),
+                _C.ptr(self.fourier.data), _C.ptr(self.fourier.grad), _C.stream_ptr())
+        return de
+
     def loss_backward(self, sv: dict) -> torch.Tensor:
         """Returns d(readout mean) (B, D) bf16 view."""
+        if sv.get("multi"):
+            return self._loss_backward_multi(sv)
         B = sv["cat"].shape[0]
         dpred = sv["dpred"]
         for (d1, d2), (x, h) in reversed(list(zip(self.extra, sv.get("chain") or []))):
@@ -377,6 +497,11 @@ class DiffusionActionHead(Bindable):
     def time_embeddings(self, device) -> torch.Tensor:
         """FourierFeatures (:41-51) + its MLPBlock for every t = 0..steps-1 -> (steps, T) bf16,
         through the training path's kernels (prep kernel with injected t, two GEMMs)."""
+        return self._time_embeddings_saved(device)[0]
+
+    def _time_embeddings_saved(self, device):
+        """time_embeddings with what its backward needs: (temb (steps, T) bf16, the Fourier
+        features (steps, T) bf16, the time MLP's hidden layer (steps, T) bf16, t = arange(steps))."""
         S, A = self.steps, self.A
         t_in = torch.arange(S, dtype=torch.int32, device=device)
         zeros = torch.zeros((S, A), dtype=torch.float32, device=device)
@@ -389,7 +514,7 @@ class DiffusionActionHead(Bindable):
                 _C.ptr(eps_out), _C.ptr(scratch), scratch.stride(0), _C.ptr(feats),
                 _C.stream_ptr())
         ht = self.t1.fwd(feats, act=K.ACT_RELU)
-        return self.t2.fwd(ht)
+        return self.t2.fwd(ht), feats, ht, t_in
 
     def sampler_table(self, spec=None):
         """The update table of `spec` (default: the head's): (t int32 (K,), coef fp32 (K, 3)) numpy

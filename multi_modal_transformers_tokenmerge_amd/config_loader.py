@@ -19,7 +19,8 @@ which are not available on the GPU box.
   key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``readout_pooling`` ("mean" |
   "attention": MultiHeadAttentionPooling of the readouts in the diffusion head, with
   ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node),
-  ``action_heads.action_horizon`` (the diffusion head denoises a chunk of that many actions) and
+  ``action_heads.action_horizon`` (the diffusion head denoises a chunk of that many actions),
+  ``action_heads.n_diffusion_samples`` (independent (t, eps) draws per sample in its loss) and
   ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``fp8_matmul``,
   ``t5_num_layers`` and ``text_tokens``.
 
@@ -295,6 +296,7 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
         kw["pooling_norm_axes"] = tuple(int(v) for v in (axes if isinstance(axes, (list, tuple))
                                                          else [axes]))
     kw["action_horizon"] = int(heads_cfg.get("action_horizon", 1))
+    kw["n_diffusion_samples"] = int(heads_cfg.get("n_diffusion_samples", 1))
     sampler = heads_cfg.get("sampler")
     kw["sampler"] = None if sampler is None else dict(sampler)
     t5_layers = cfg.get("t5_num_layers")

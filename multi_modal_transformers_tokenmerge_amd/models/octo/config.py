@@ -83,8 +83,15 @@ class OctoConfig:
     # the diffusion head's default sampler: the fields of action_heads.diffusion.SamplerSpec as a
     # dict (YAML key action_heads.sampler), None = the reference's 32-step loop
     sampler: Optional[dict] = None
+    # independent (t, eps) draws per sample in the diffusion loss, against one backbone forward
+    # (upstream Octo's n_diffusion_samples; YAML key action_heads.n_diffusion_samples), 1 .. 64.
+    # Above 1 the loss runs the fused multi-draw kernel (DiffusionActionHead.loss_forward_multi)
+    n_diffusion_samples: int = 1
 
     def __post_init__(self):
+        n = self.n_diffusion_samples
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 64:
+            raise ValueError(f"n_diffusion_samples must be an integer in 1 .. 64, got {n!r}")
         if self.action_horizon < 1:
             raise ValueError(f"action_horizon must be >= 1, got {self.action_horizon}")
         if self.action_horizon > 1 and set(self.action_heads) - {"diffusion"}:

@@ -104,7 +104,8 @@ class Octo:
         self.head = DiffusionActionHead.create(store, "diffusion_action_head", D,
                                                cfg.action_space_dim * cfg.action_horizon,
                                                cfg.diffusion_steps,
-                                               num_blocks=cfg.denoise_blocks, sampler=cfg.sampler)
+                                               num_blocks=cfg.denoise_blocks, sampler=cfg.sampler,
+                                               n_diffusion_samples=cfg.n_diffusion_samples)
         self.continuous_head = self.categorical_head = None
         if "continuous" in cfg.action_heads:
             self.continuous_head = ContinuousActionHead(store, "continuous_action_head", D,
@@ -283,28 +284,52 @@ class Octo:
         return {si: MergeSource(buf.clone(), t) for si, (buf, t) in sorted(maps.items())}
 
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
-                                       sample_offset=0, inject: Optional[dict] = None, t5_out=None):
+                                       sample_offset=0, inject: Optional[dict] = None, t5_out=None,
+                                       action_pad_mask=None):
         """Reference :139-145. Returns (loss (1,) fp32 device tensor, saved state). inject (tests):
         positions (rt, ct), t, eps, tome (per block an (unm, src, dst) triple of int32 device
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
-        output for text_tokens computed ahead (generate_readouts)."""
+        output for text_tokens computed ahead (generate_readouts).
+        action_pad_mask: bool (B, action_horizon, action_space_dim) or (B, h a), True where an
+        action component is real: padded chunk steps / action dimensions do not enter the loss,
+        which is normalised by the number of real components. With it, or with
+        OctoConfig.n_diffusion_samples = K > 1 (K independent (t, eps) draws per sample; inject
+        t (K, B) / eps (K, B, h a)), the head runs its fused multi-draw loss on the pooled readout
+        (DiffusionActionHead.loss_forward_multi)."""
         inject = inject or {}
         actions = self._chunk_flat(actions)
+        multi = self.cfg.n_diffusion_samples > 1 or action_pad_mask is not None
+        if action_pad_mask is not None:
+            if action_pad_mask.dtype != torch.bool:
+                raise ValueError("action_pad_mask must be a bool tensor")
+            action_pad_mask = self._chunk_flat(action_pad_mask)
+            if action_pad_mask.shape[0] != actions.shape[0]:
+                raise ValueError("action_pad_mask and actions differ in batch size")
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         inject.get("positions"), inject.get("tome"), t5_out)
         B = xL.shape[0]
-        cat = self.head.new_cat(B, xL.device)
+        if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
+            cat = None
+            pooled = torch.empty((B, self.D), dtype=torch.bfloat16, device=xL.device)
+        else:
+            cat = self.head.new_cat(B, xL.device)
+            pooled = self.head.readout_slot(cat)
         if self.pooling is not None:
             with phase("fwd/pool"):
-                _, st["pool_sv"] = self.pooling.forward(xL, self.readout_rows,
-                                                        out=self.head.readout_slot(cat))
+                _, st["pool_sv"] = self.pooling.forward(xL, self.readout_rows, out=pooled)
         else:
             _C.call("mmt_rows_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.D,
                     _C.ptr(self.readout_rows), self.readout_rows.numel(),
-                    _C.ptr(self.head.readout_slot(cat)), cat.stride(0), _C.stream_ptr())
+                    _C.ptr(pooled), pooled.stride(0), _C.stream_ptr())
         with phase("fwd/head"):
-            loss, hsv = self.head.loss_forward(cat, actions, rng, sample_offset, inject.get("t"),
-                                               inject.get("eps"))
+            if multi:
+                loss, hsv = self.head.loss_forward_multi(
+                    pooled, actions.float().contiguous(), rng, sample_offset,
+                    self.cfg.n_diffusion_samples, action_pad_mask, inject.get("t"),
+                    inject.get("eps"))
+            else:
+                loss, hsv = self.head.loss_forward(cat, actions, rng, sample_offset,
+                                                   inject.get("t"), inject.get("eps"))
         st.update(head_sv=hsv, xL_shape=tuple(xL.shape), xL=xL)
         return loss, st
 
@@ -990,10 +1015,11 @@ def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                         inject: Optional[dict] = None):
+                         inject: Optional[dict] = None, action_pad_mask=None):
     """Reference octo.py:204-240: value_and_grad of the denoise loss, apply_gradients, metrics
     merge. Returns (train_state, grads) like the reference; grads are views of the flat gradient
     buffer by parameter name, the loss is train_state.last_loss (device) and the running average
-    train_state.metrics."""
+    train_state.metrics. action_pad_mask: compute_diffusion_denoise_loss's."""
+    kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
     return _train_step(model.compute_diffusion_denoise_loss, model, train_state, text_tokens,
-                       images, actions, inject=inject)
+                       images, actions, inject=inject, **kw)
