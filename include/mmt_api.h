@@ -903,6 +903,69 @@ int mmt_action_head(int kind, const float* z, int64_t ldz, int R, int N, const f
                     const float* edges, int n_edges, float max_action, float inv_count, float* pred,
                     float* loss, void* dz, mmt_stream_t stream);
 
+/* ---- action chunks, pad mask and decoding (csrc/heads.hip). mmt_action_head above stays the path
+ * of one action, no mask, squared error; these three entries take a chunk of h actions per sample,
+ * a pad mask and (categorical) the way back from logits to an action. Common contract: one wave
+ * per row, four rows per 256-thread workgroup; graph-capturable, allocate nothing, no host
+ * synchronisation and no float atomics: every row writes an fp32 loss partial into `scratch`, a
+ * first small launch counts the mask's ones with integer adds into scratch[0] (the element count
+ * without a mask), and a last one-workgroup launch adds the partials in a fixed order: thread t of
+ * 256 adds the partials t, t + 256, t + 512, ... in ascending order, then the 256 sums are folded
+ * in halves (s[t] += s[t + 128], then 64, ... 1), and the normalisation is applied from the
+ * device-side count. Two calls on the same inputs agree bit for bit. loss[0] is overwritten.
+ * scratch: rows + 1 fp32 words of the caller. The normalisation is the diffusion head's masked
+ * one (mmt_diffusion_loss_multi): width / max(sum m, 1) times the masked sum, so an all-ones mask
+ * reproduces the unmasked mean and an all-zero mask gives loss 0 and zero gradients.
+ *
+ * mmt_head_continuous: ContinuousActionHead (continuous.py:19-26, the axis `seq` of :24 at its
+ * general value h) + compute_l2_loss (octo.py:167-174) with the train step's mean (:262). Rows
+ * are the B samples, width W = h A (step-major, component a of step s at s A + a), 1 <= W <= 4096;
+ * z fp32 with row stride ldz >= W. p = tanh(z / max_action) max_action, written to pred (B, W)
+ * fp32 if non-NULL. With targets y (B, W) fp32 and the optional mask m (B, W) uint8 (non-zero:
+ * the component counts; NULL: all ones): e = (p - y)^2 (loss_kind MMT_HEAD_LOSS_MSE) or |p - y|
+ * (MMT_HEAD_LOSS_L1, upstream Octo's default regression loss);
+ *   loss = A / max(sum m, 1) sum m e   (no mask: the mean over (b, step) of sum_a e)
+ *   dz   = A / max(sum m, 1) m e'(p - y) (1 - tanh^2)   bf16 (B, W), e' = 2 d or sign(d), sign(0) = 0
+ * y NULL: forward only (pred is required; m, loss, dz, scratch must be NULL or are ignored, a mask
+ * without targets is MMT_ERR_INVALID). */
+enum { MMT_HEAD_LOSS_MSE = 0, MMT_HEAD_LOSS_L1 = 1 };
+int mmt_head_continuous(const float* z, int64_t ldz, int B, int h, int A, const float* y,
+                        const uint8_t* mask, int loss_kind, float max_action, float* pred,
+                        float* scratch, float* loss, void* dz, mmt_stream_t stream);
+/* mmt_head_categorical: CategoricalActionHead logits (categorical.py:25-40, the axis `action` of
+ * :32-36 at h A groups) + compute_ce_loss (octo.py:187-198) with the train step's mean (:302).
+ * Rows are the R = B h A (sample, step, component) groups, width N = num_bins, 2 <= N <= 1024; z
+ * fp32 (R, N) with row stride ldz >= N; y (R,) fp32; the optional row mask m (R,) uint8. Labels as
+ * kind 1 of mmt_action_head: bin = #edges <= y (edges (n_edges,) fp32, n_edges = N + 1 of
+ * assign_bins, categorical.py:12-22), one_hot(bin, N) all zero for bin >= N (the reference's
+ * off-by-one kept: such a row adds 0 to the loss and still counts in the denominator);
+ *   loss = sum m ce / max(sum m, 1);   dz = m (has softmax(z) - label) / max(sum m, 1)   bf16 (R, N)
+ * cls (R,) int32, optional: the argmax class of every row, the first index on ties (jnp.argmax).
+ * y is required (a mask without targets is MMT_ERR_INVALID): the forward alone is the Dense. */
+int mmt_head_categorical(const float* z, int64_t ldz, int R, int N, const float* y,
+                         const uint8_t* mask, const float* edges, int n_edges, float* scratch,
+                         float* loss, void* dz, int32_t* cls, mmt_stream_t stream);
+/* mmt_head_categorical_decode: logits back to actions, the inverse of assign_bins that the
+ * reference stops short of (octo.py:178-185 ends at the logits). z (R, N) fp32 (row stride ldz),
+ * 2 <= N <= 1024; values (N,) fp32, the action each class stands for (action_heads/categorical.py
+ * bin_values). Writes cls (R,) int32 and actions (R,) fp32 = values[cls].
+ * mode MMT_DECODE_ARGMAX: the largest logit, the first index on ties.
+ * mode MMT_DECODE_SAMPLE: one draw per row from softmax(z / temperature), temperature > 0, by
+ * inverse CDF: key stream_key(seed, step, 0xFFF8, 1) of rng = {seed, step} (layer word 0xFFF8 is
+ * this entry's alone: 0xFFF9 .. 0xFFFF are taken, see mmt_diffusion_loss_multi), counter
+ * (sample_offset + b) G + g for row r = b G + g (G = h A groups per sample, R % G == 0);
+ * u = ((draw_u32 >> 8) + 0.5) / 2^24 in fp32 (the sum is exact below 2^23 and rounds to even
+ * above, so u lies in (0, 1]; oracle/rng.py restates the draw bit for bit); the class is the
+ * smallest c with CDF(c) > u, N - 1 if there is none. The prefix sum stays in the wave: lane l
+ * holds the contiguous classes [l n, (l + 1) n), n = ceil(N / 64), adds their exp((z - max) /
+ * temperature) in ascending order, an exclusive scan over the lanes gives each run's start, and
+ * CDF(c) > u is tested as prefix(c) > u total (no division). rng may be NULL in argmax mode. */
+enum { MMT_DECODE_ARGMAX = 0, MMT_DECODE_SAMPLE = 1 };
+int mmt_head_categorical_decode(const float* z, int64_t ldz, int R, int N, int G,
+                                const float* values, int mode, float temperature,
+                                const uint32_t* rng, int64_t sample_offset, int32_t* cls,
+                                float* actions, mmt_stream_t stream);
+
 /* ------------------------------------------------------------------ T5 encoder pieces
  * (tokenizers/text/t5_base.py:8-15, frozen FlaxT5 encoder): T5LayerNorm and the shared
  * embedding lookup. bf16 rows of D elements, D > 0, D % 8 == 0, moved as 16-B vectors: x, w, y

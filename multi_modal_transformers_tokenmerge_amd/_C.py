@@ -112,6 +112,9 @@ SIGNATURES: dict[str, list] = {
     "mmt_rows_group_mean_fwd": [P, L, L, I, I, I, P, I, P, P, P],
     "mmt_rows_group_mean_bwd": [P, I, I, I, P, I, P, P, P],
     "mmt_action_head": [I, P, L, I, I, P, P, I, F, F, P, P, P, P],
+    "mmt_head_continuous": [P, L, I, I, I, P, P, I, F, P, P, P, P, P],
+    "mmt_head_categorical": [P, L, I, I, P, P, P, I, P, P, P, P, P],
+    "mmt_head_categorical_decode": [P, L, I, I, I, P, I, F, P, L, P, P, P],
     "mmt_rmsnorm_fwd": [P, L, I, P, F, P, P],
     "mmt_embedding_gather": [P, L, I, P, I, P, P],
     "mmt_adamw": [P, P, P, P, P, L, P, D, D, D, D, D, F, P],
@@ -306,6 +309,10 @@ def diffusion_loss_route(A: int, H: int) -> int:
 
 def diffusion_loss_last_route() -> int:
     return call("mmt_diffusion_loss_last_route")
+
+
+HEAD_LOSS_MSE, HEAD_LOSS_L1 = 0, 1   # MMT_HEAD_LOSS_* (mmt_head_continuous loss_kind)
+DECODE_ARGMAX, DECODE_SAMPLE = 0, 1  # MMT_DECODE_* (mmt_head_categorical_decode mode)
 
 
 def workspace_size(op: int, *dims: int) -> int:

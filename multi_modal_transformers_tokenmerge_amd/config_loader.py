@@ -21,7 +21,9 @@ which are not available on the GPU box.
   ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node),
   ``action_heads.action_horizon`` (the diffusion head denoises a chunk of that many actions),
   ``action_heads.n_diffusion_samples`` (independent (t, eps) draws per sample in its loss) and
-  ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``fp8_matmul``,
+  ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``action_heads.pred_horizon``
+  (the chunk length of the continuous and categorical heads) and
+  ``action_heads.continuous_loss`` ("mse" | "l1"), ``fp8_matmul``,
   ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
@@ -297,6 +299,8 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
                                                          else [axes]))
     kw["action_horizon"] = int(heads_cfg.get("action_horizon", 1))
     kw["n_diffusion_samples"] = int(heads_cfg.get("n_diffusion_samples", 1))
+    kw["pred_horizon"] = int(heads_cfg.get("pred_horizon", 1))
+    kw["continuous_loss"] = str(heads_cfg.get("continuous_loss", "mse"))
     sampler = heads_cfg.get("sampler")
     kw["sampler"] = None if sampler is None else dict(sampler)
     t5_layers = cfg.get("t5_num_layers")

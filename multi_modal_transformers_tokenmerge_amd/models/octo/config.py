@@ -78,8 +78,17 @@ class OctoConfig:
     pooling_norm_axes: tuple = (-1,)
     # action chunking (Octo / Diffusion Policy): the diffusion head denoises action_horizon
     # consecutive actions at once, so its width is action_space_dim * action_horizon (YAML key
-    # action_heads.action_horizon). The continuous and categorical heads predict one action.
+    # action_heads.action_horizon). The continuous and categorical heads have a chunk length of
+    # their own, pred_horizon (YAML key action_heads.pred_horizon, default 1: one action, the
+    # reference's `seq=1` of continuous.py:24): the continuous Dense is D -> pred_horizon *
+    # action_space_dim and the categorical head forms pred_horizon * action_space_dim readout
+    # groups, step-major. With action_horizon > 1 beside one of these heads the two must agree
+    # (one dataset chunk feeds every head); action_horizon = 1 with pred_horizon > 1 is allowed.
     action_horizon: int = 1
+    pred_horizon: int = 1
+    # the continuous head's regression loss (YAML key action_heads.continuous_loss): "mse" (the
+    # reference's compute_l2_loss) or "l1" (upstream Octo's default)
+    continuous_loss: str = "mse"
     # the diffusion head's default sampler: the fields of action_heads.diffusion.SamplerSpec as a
     # dict (YAML key action_heads.sampler), None = the reference's 32-step loop
     sampler: Optional[dict] = None
@@ -94,9 +103,17 @@ class OctoConfig:
             raise ValueError(f"n_diffusion_samples must be an integer in 1 .. 64, got {n!r}")
         if self.action_horizon < 1:
             raise ValueError(f"action_horizon must be >= 1, got {self.action_horizon}")
-        if self.action_horizon > 1 and set(self.action_heads) - {"diffusion"}:
+        ph = self.pred_horizon
+        if isinstance(ph, bool) or not isinstance(ph, int) or ph < 1:
+            raise ValueError(f"pred_horizon must be an integer >= 1, got {ph!r}")
+        if self.continuous_loss not in ("mse", "l1"):
+            raise ValueError(f"continuous_loss must be 'mse' or 'l1', got {self.continuous_loss!r}")
+        if self.action_horizon > 1 and set(self.action_heads) - {"diffusion"} \
+                and ph != self.action_horizon:
             raise ValueError("action_horizon > 1 is the diffusion head's: the continuous and "
-                             f"categorical heads predict one action, got heads {self.action_heads}")
+                             "categorical heads predict pred_horizon actions, which must equal "
+                             f"action_horizon {self.action_horizon} beside them, got pred_horizon "
+                             f"{ph} with heads {self.action_heads}")
         if self.sampler is not None:
             from ...action_heads.diffusion import SamplerSpec
             SamplerSpec.of(self.sampler)     # ValueError on a bad spec

@@ -35,7 +35,7 @@ import torch
 from ... import _C, _kernels as K
 from ...tracing import phase
 from ...action_heads.categorical import CategoricalActionHead
-from ...action_heads.continuous import ContinuousActionHead
+from ...action_heads.continuous import ContinuousActionHead, chunk_flat
 from ...action_heads.diffusion import DiffusionActionHead
 from ...attention_blocks.attention import (LayerCtx, MultiHeadAttentionPooling,
                                            StackedEncoder1DBlock)
@@ -109,11 +109,13 @@ class Octo:
         self.continuous_head = self.categorical_head = None
         if "continuous" in cfg.action_heads:
             self.continuous_head = ContinuousActionHead(store, "continuous_action_head", D,
-                                                        cfg.action_space_dim, cfg.max_action)
+                                                        cfg.action_space_dim, cfg.max_action,
+                                                        horizon=cfg.pred_horizon,
+                                                        loss=cfg.continuous_loss)
         if "categorical" in cfg.action_heads:
             self.categorical_head = CategoricalActionHead(store, "categorical_action_head", D,
                                                           cfg.action_space_dim, cfg.num_bins,
-                                                          cfg.max_action)
+                                                          cfg.max_action, horizon=cfg.pred_horizon)
         # readout pooling by attention (OctoConfig.readout_pooling): declared after every head, so
         # the offsets of all the parameters above are those of the "mean" configuration
         self.pooling = None
@@ -199,16 +201,17 @@ class Octo:
         flag = np.full(self.L_final, -1, np.int32)
         flag[rows] = np.arange(len(rows))
         self.readout_flag = torch.from_numpy(flag).to(self.device)
-        # categorical head: readout i belongs to action i // (n / A) ("batch (action timestep)
-        # embeddings", categorical.py:32-36)
-        A = cfg.action_space_dim
+        # categorical head: readout i belongs to group i // (n / G) ("batch (action timestep)
+        # embeddings", categorical.py:32-36), G = pred_horizon * action_space_dim groups,
+        # step-major (group g = step * A + a)
+        G = self.n_groups = cfg.pred_horizon * cfg.action_space_dim
         self.readout_group = self.readout_group_counts = None
-        if len(rows) % A == 0:
-            per = len(rows) // A
+        if len(rows) % G == 0:
+            per = len(rows) // G
             grp = np.full(self.L_final, -1, np.int32)
             grp[rows] = np.arange(len(rows)) // per
             self.readout_group = torch.from_numpy(grp).to(self.device)
-            self.readout_group_counts = torch.full((A,), per, dtype=torch.int32, device=self.device)
+            self.readout_group_counts = torch.full((G,), per, dtype=torch.int32, device=self.device)
 
     def layer_ctxs(self, train: bool, rng, sample_offset: int) -> List[LayerCtx]:
         prop = bool(self.cfg.proportional_attention)
@@ -333,20 +336,12 @@ class Octo:
         st.update(head_sv=hsv, xL_shape=tuple(xL.shape), xL=xL)
         return loss, st
 
-    def _chunk_flat(self, actions):
-        """The diffusion head's view of an action chunk: (B, action_horizon, action_space_dim) or
-        the already flat (B, action_horizon * action_space_dim), as (B, h a). A flat tensor is
-        returned as it is."""
-        h, a = self.cfg.action_horizon, self.cfg.action_space_dim
-        if actions.dim() == 3:
-            if tuple(actions.shape[1:]) != (h, a):
-                raise ValueError(f"actions must be (B, {h}, {a}) or (B, {h * a}), got "
-                                 f"{tuple(actions.shape)}")
-            return actions.reshape(actions.shape[0], h * a)
-        if actions.dim() != 2 or actions.shape[1] != h * a:
-            raise ValueError(f"actions must be (B, {h}, {a}) or (B, {h * a}), got "
-                             f"{tuple(actions.shape)}")
-        return actions
+    def _chunk_flat(self, actions, horizon: Optional[int] = None):
+        """A head's view of an action chunk: (B, h, action_space_dim) or the already flat
+        (B, h * action_space_dim), as (B, h a); h = `horizon`, None: the diffusion head's
+        action_horizon. A flat tensor is returned as it is."""
+        h = self.cfg.action_horizon if horizon is None else horizon
+        return chunk_flat(actions, h, self.cfg.action_space_dim)
 
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
                                        sample_offset=0, train=True):
@@ -398,12 +393,13 @@ class Octo:
 
     def _readout_group_means(self, xL):
         if self.readout_group is None:
-            raise ValueError("the readout count must be a multiple of action_space_dim "
+            raise ValueError(f"the readout count {self.readout_rows.numel()} must be a multiple "
+                             f"of pred_horizon * action_space_dim = {self.n_groups} "
                              "(categorical.py:32-36)")
-        B, A = xL.shape[0], self.cfg.action_space_dim
-        g = torch.empty((B, A, self.D), dtype=torch.bfloat16, device=xL.device)
+        B, G = xL.shape[0], self.n_groups
+        g = torch.empty((B, G, self.D), dtype=torch.bfloat16, device=xL.device)
         _C.call("mmt_rows_group_mean_fwd", _C.ptr(xL), xL.stride(0), xL.stride(1), B, self.L_final,
-                self.D, _C.ptr(self.readout_group), A, _C.ptr(self.readout_group_counts), _C.ptr(g),
+                self.D, _C.ptr(self.readout_group), G, _C.ptr(self.readout_group_counts), _C.ptr(g),
                 _C.stream_ptr())
         return g
 
@@ -413,30 +409,56 @@ class Octo:
         return head
 
     def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True):
-        """Reference :158-165 -> (B, 1, A) fp32."""
+        """Reference :158-165 -> (B, pred_horizon, A) fp32 ((B, 1, A) as the reference)."""
         h = self._need(self.continuous_head, "continuous")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
         return h.forward(self._readout_mean(xL))
 
-    def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0):
-        """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved)."""
+    @staticmethod
+    def _check_pad_mask(action_pad_mask):
+        if action_pad_mask is not None and action_pad_mask.dtype != torch.bool:
+            raise ValueError("action_pad_mask must be a bool tensor")
+
+    def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
+                        action_pad_mask=None):
+        """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved).
+        actions (B, pred_horizon, A) or flat; OctoConfig.continuous_loss picks the squared error
+        or L1. action_pad_mask: bool, the actions' shape, True where a component is real: padded
+        chunk steps / action dimensions do not enter the loss, which is normalised by the number
+        of real components (as compute_diffusion_denoise_loss)."""
         h = self._need(self.continuous_head, "continuous")
+        self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
-        loss, hsv = h.loss_forward(self._readout_mean(xL), actions)
+        loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
     def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True):
-        """Reference :178-185 -> (B, A, num_bins) fp32."""
+        """Reference :178-185 -> (B, A, num_bins) fp32, (B, pred_horizon, A, num_bins) with a
+        pred_horizon > 1."""
         h = self._need(self.categorical_head, "categorical")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
         return h.forward(self._readout_group_means(xL))
 
-    def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0):
-        """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved)."""
+    def predict_categorical_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
+                                   mode="argmax", temperature=1.0):
+        """The categorical head rolled out: logits (predict_action_logits) decoded to actions
+        (B, pred_horizon, A) fp32 through bin_values, by argmax or (mode "sample") one draw per
+        component from softmax(logits / temperature) keyed by rng and sample_offset
+        (CategoricalActionHead.decode)."""
         h = self._need(self.categorical_head, "categorical")
+        logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train)
+        return h.decode(logits, rng, sample_offset, mode, temperature)[0]
+
+    def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
+                        action_pad_mask=None):
+        """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved).
+        actions (B, pred_horizon, A) or flat. action_pad_mask: compute_l2_loss's; the loss is the
+        mean of the cross entropy over the real components."""
+        h = self._need(self.categorical_head, "categorical")
+        self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
-        loss, hsv = h.loss_forward(self._readout_group_means(xL), actions)
+        loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
@@ -621,7 +643,7 @@ class Octo:
                 return None
             dxL = torch.empty(st["xL_shape"], dtype=torch.float32, device=dg.device)
             _C.call("mmt_rows_group_mean_bwd", _C.ptr(dg), B, self.L_final, D,
-                    _C.ptr(self.readout_group), self.cfg.action_space_dim,
+                    _C.ptr(self.readout_group), self.n_groups,
                     _C.ptr(self.readout_group_counts), _C.ptr(dxL), _C.stream_ptr())
         else:
             head = self.continuous_head if kind == "continuous" else self.head
@@ -1002,16 +1024,22 @@ def _train_step(loss_fn, model: Octo, train_state: OCTOTrainState, text_tokens, 
     return train_state, grads_tree(model)
 
 
-def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions):
+def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
+                          action_pad_mask=None):
     """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads)."""
-    return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions)
+    metrics merge. Returns (train_state, grads). action_pad_mask: compute_l2_loss's."""
+    kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
+    return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions,
+                       **kw)
 
 
-def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions):
+def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
+                           action_pad_mask=None):
     """Reference octo.py:282-320: value_and_grad of mean(compute_ce_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads)."""
-    return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions)
+    metrics merge. Returns (train_state, grads). action_pad_mask: compute_ce_loss's."""
+    kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
+    return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions,
+                       **kw)
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
