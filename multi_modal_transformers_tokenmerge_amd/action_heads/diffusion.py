@@ -350,11 +350,21 @@ class DiffusionActionHead(Bindable):
         if self.extra:
             raise ValueError("n_diffusion_samples > 1 and pad_mask need OctoDenoise num_blocks == 1 "
                              "(the fused loss holds one MLPBlock, as the fused sampler does)")
-        if self.A % 8 or not 8 <= self.A <= 64:
-            raise ValueError(f"the fused loss needs an action width in 8, 16 .. 64, got {self.A}")
-        if self.hidden % 8 or self.hidden > 1024:
-            raise ValueError("the fused loss needs a hidden width that is a multiple of 8, at "
+        self._check_fused_widths("fused loss")
+
+    def _check_fused_widths(self, what: str, action: bool = True, hidden: bool = True):
+        """The widths of the fused kernels (csrc/denoiser_wave.h): A in 8, 16 .. 64 (`action`;
+        the loop sampler's draws need that too) and H a multiple of 8 up to 1024 (`hidden`)."""
+        if action and (self.A % 8 or not 8 <= self.A <= 64):
+            raise ValueError(f"the {what} needs an action width in 8, 16 .. 64, got {self.A}")
+        if hidden and (self.hidden % 8 or self.hidden > 1024):
+            raise ValueError(f"the {what} needs a hidden width that is a multiple of 8, at "
                              f"most 1024, got {self.hidden}")
+
+    def _check_pooled(self, e: torch.Tensor, name: str):
+        """The pooled readout of the fused loss and the samplers."""
+        if e.dim() != 2 or e.shape[1] != self.D or e.dtype != torch.bfloat16 or e.stride(1) != 1:
+            raise ValueError(f"{name} must be bf16 (B, {self.D}) with unit inner stride")
 
     def loss_forward_multi(self, e: torch.Tensor, actions: torch.Tensor, rng, sample_offset: int = 0,
                            K: int = 1, pad_mask=None, t_in=None, eps_in=None, backward: bool = True):
@@ -367,8 +377,7 @@ class DiffusionActionHead(Bindable):
         backward=False: forward only (evaluation). Returns (loss (1,) fp32, saved)."""
         self._check_multi(K)
         B, A, H, S, dev = e.shape[0], self.A, self.hidden, self.steps, e.device
-        if e.dim() != 2 or e.shape[1] != self.D or e.dtype != torch.bfloat16 or e.stride(1) != 1:
-            raise ValueError(f"the pooled readout must be bf16 (B, {self.D}) with unit inner stride")
+        self._check_pooled(e, "the pooled readout")
         if tuple(actions.shape) != (B, A) or actions.dtype != torch.float32 \
                 or not actions.is_contiguous():
             raise ValueError(f"actions must be contiguous fp32 ({B}, {A})")
@@ -386,11 +395,10 @@ class DiffusionActionHead(Bindable):
                 raise ValueError(f"injected eps must be contiguous fp32 ({K}, {B}, {A})")
         elif rng is None:
             raise ValueError("need the diffusion rng (or injected t and eps)")
-        temb, feats, ht, t_all = self._time_embeddings_saved(dev)
+        saved = self._time_embeddings_saved(dev)
+        temb, feats, ht, t_all = saved
+        P, Q = self._split_first_dense(e, saved)
         w1 = self.d1.w.bf16
-        Q = K_.gemm(temb, w1[:, A:A + self.time_dim], trans_b=True, bias=self.d1.b.data,
-                    out_mode=K_.OUT_F32)
-        P = K_.gemm(e, w1[:, A + self.time_dim:], trans_b=True, out_mode=K_.OUT_F32)
         bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev) if backward else None
         t = torch.empty((K, B), dtype=torch.int32, device=dev)
         eps = torch.empty((K, B, A), dtype=torch.float32, device=dev)
@@ -466,14 +474,7 @@ class DiffusionActionHead(Bindable):
         if readout_mean.shape[1] != self.D or readout_mean.dtype != torch.bfloat16:
             raise ValueError(f"readout_mean must be bf16 (B, {self.D})")
         cat = self.new_cat(B, dev)
-        zeros = torch.zeros((B, self.A), dtype=torch.float32, device=dev)
-        feats = torch.empty((B, self.time_dim), dtype=torch.bfloat16, device=dev)
-        t_out = torch.empty(B, dtype=torch.int32, device=dev)
-        eps_out = torch.empty((B, self.A), dtype=torch.float32, device=dev)
-        _C.call("mmt_diffusion_prep", None, B, self.A, self.steps, 0, _C.ptr(zeros),
-                _C.ptr(self.consts(dev)), _C.ptr(self.fourier.data), self.F, _C.ptr(t),
-                _C.ptr(zeros), _C.ptr(t_out), _C.ptr(eps_out), _C.ptr(cat), cat.stride(0),
-                _C.ptr(feats), _C.stream_ptr())
+        feats = self._fourier_features(t, cat)
         cat[:, :self.A].copy_(noisy_actions)           # the given noisy sample (bf16 operand)
         self.readout_slot(cat).copy_(readout_mean)
         ht = self.t1.fwd(feats, act=K.ACT_RELU)
@@ -502,19 +503,25 @@ class DiffusionActionHead(Bindable):
     def _time_embeddings_saved(self, device):
         """time_embeddings with what its backward needs: (temb (steps, T) bf16, the Fourier
         features (steps, T) bf16, the time MLP's hidden layer (steps, T) bf16, t = arange(steps))."""
-        S, A = self.steps, self.A
-        t_in = torch.arange(S, dtype=torch.int32, device=device)
-        zeros = torch.zeros((S, A), dtype=torch.float32, device=device)
-        scratch = self.new_cat(S, device)
-        feats = torch.empty((S, self.time_dim), dtype=torch.bfloat16, device=device)
-        t_out = torch.empty(S, dtype=torch.int32, device=device)
-        eps_out = torch.empty((S, A), dtype=torch.float32, device=device)
-        _C.call("mmt_diffusion_prep", None, S, A, S, 0, _C.ptr(zeros), _C.ptr(self.consts(device)),
-                _C.ptr(self.fourier.data), self.F, _C.ptr(t_in), _C.ptr(zeros), _C.ptr(t_out),
-                _C.ptr(eps_out), _C.ptr(scratch), scratch.stride(0), _C.ptr(feats),
-                _C.stream_ptr())
+        t_in = torch.arange(self.steps, dtype=torch.int32, device=device)
+        feats = self._fourier_features(t_in, self.new_cat(self.steps, device))
         ht = self.t1.fwd(feats, act=K.ACT_RELU)
         return self.t2.fwd(ht), feats, ht, t_in
+
+    def _fourier_features(self, t: torch.Tensor, cat: torch.Tensor) -> torch.Tensor:
+        """The Fourier features (n, T) bf16 of the given steps t (n,) int32 from the training
+        path's prep kernel, run with zero actions and injected (t, eps = 0); it also writes cat's
+        action columns (n, A+T+D) bf16 (zeros)."""
+        n, dev = t.shape[0], t.device
+        zeros = torch.zeros((n, self.A), dtype=torch.float32, device=dev)
+        feats = torch.empty((n, self.time_dim), dtype=torch.bfloat16, device=dev)
+        t_out = torch.empty(n, dtype=torch.int32, device=dev)
+        eps_out = torch.empty((n, self.A), dtype=torch.float32, device=dev)
+        _C.call("mmt_diffusion_prep", None, n, self.A, self.steps, 0, _C.ptr(zeros),
+                _C.ptr(self.consts(dev)), _C.ptr(self.fourier.data), self.F, _C.ptr(t),
+                _C.ptr(zeros), _C.ptr(t_out), _C.ptr(eps_out), _C.ptr(cat), cat.stride(0),
+                _C.ptr(feats), _C.stream_ptr())
+        return feats
 
     def sampler_table(self, spec=None):
         """The update table of `spec` (default: the head's): (t int32 (K,), coef fp32 (K, 3)) numpy
@@ -559,11 +566,12 @@ class DiffusionActionHead(Bindable):
                                      torch.from_numpy(np.ascontiguousarray(coef)).to(device), t)
         return self._dev_consts[key]
 
-    def _split_first_dense(self, readout_mean):
+    def _split_first_dense(self, readout_mean, saved=None):
         """concatenate([noisy, time_emb, readout]) . W1^T (OctoDenoise :61) split along the input:
-        P (B, H) = readout part, Q (steps, H) = time-embedding part + b1, both fp32."""
+        P (B, H) = readout part, Q (steps, H) = time-embedding part + b1, both fp32. saved: the
+        _time_embeddings_saved tuple of a caller that keeps it for its backward."""
         A, T = self.A, self.time_dim
-        temb = self.time_embeddings(readout_mean.device)
+        temb = (saved or self._time_embeddings_saved(readout_mean.device))[0]
         w1 = self.d1.w.bf16
         Q = K.gemm(temb, w1[:, A:A + T], trans_b=True, bias=self.d1.b.data, out_mode=K.OUT_F32)
         P = K.gemm(readout_mean, w1[:, A + T:], trans_b=True, out_mode=K.OUT_F32)
@@ -615,9 +623,7 @@ class DiffusionActionHead(Bindable):
         One launch either way for num_blocks == 1: the reference's sampler at A == 8 runs
         mmt_diffusion_sample, everything else mmt_diffusion_sample_steps; num_blocks > 1 takes
         the per-step launch loop."""
-        if readout_mean.dim() != 2 or readout_mean.shape[1] != self.D \
-                or readout_mean.dtype != torch.bfloat16 or readout_mean.stride(1) != 1:
-            raise ValueError(f"readout_mean must be bf16 (B, {self.D}) with unit inner stride")
+        self._check_pooled(readout_mean, "readout_mean")
         spec = self.sampler if sampler is None else SamplerSpec.of(sampler)
         if noise is not None and not spec.fresh:
             spec = dataclasses.replace(spec, noise="fresh")   # ValueError for DDIM
@@ -631,14 +637,11 @@ class DiffusionActionHead(Bindable):
             raise ValueError(f"noise must be contiguous fp32 ({K_steps}, {B}, {A})")
         if rng is None and (z is None or (spec.fresh and noise is None)):
             raise ValueError("need rng (or an injected initial sample z and step noise)")
-        if A % 8 or not 8 <= A <= 64:     # the fused kernels, and the loop form's draws
-            raise ValueError(f"the sampler needs an action width in 8, 16 .. 64, got {A}")
+        self._check_fused_widths("sampler", hidden=False)   # the loop form's draws need A too
         if self.extra:
             return self._predict_action_loop(readout_mean, rng, sample_offset, z, return_noise,
                                              spec=spec, noise=noise)
-        if self.hidden % 8 or self.hidden > 1024:
-            raise ValueError("the fused sampler needs a hidden width that is a multiple of 8, at "
-                             f"most 1024, got {self.hidden}")
+        self._check_fused_widths("fused sampler", action=False)
         if not (spec.is_reference(self.steps) and A == 8 and noise is None):
             actions, z_out, n_out = self._sample_steps(readout_mean, rng, sample_offset, z, noise,
                                                        spec, want_z=return_noise,

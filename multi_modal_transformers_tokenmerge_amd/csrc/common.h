@@ -82,6 +82,14 @@ __host__ __device__ __forceinline__ uint32_t stream_key(uint32_t seed, uint32_t 
 __host__ __device__ __forceinline__ uint32_t draw_u32(uint32_t key, uint32_t ctr) {
   return mix32(key ^ mix32(ctr));
 }
+// N(0, 1) by Box-Muller from draws 2 c and 2 c + 1 of a stream (24-bit uniforms): every Gaussian of
+// the diffusion head (training eps, the samplers' z and step noise), so equal keys and counters
+// give equal bits in every kernel.
+__device__ __forceinline__ float normal_draw(uint32_t key, uint32_t c) {
+  const float u1 = ((draw_u32(key, 2 * c) >> 8) + 1) * (1.f / 16777216.f);  // (0, 1]
+  const float u2 = (draw_u32(key, 2 * c + 1) >> 8) * (1.f / 16777216.f);
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
 // keep-probability threshold: keep iff draw < thresh, thresh = floor(keep_prob * 2^32)
 __host__ __device__ __forceinline__ bool keep_draw(uint32_t key, uint32_t ctr, uint32_t thresh) {
   return draw_u32(key, ctr) < thresh;
@@ -257,5 +265,12 @@ __device__ __forceinline__ int checked_index(int v, int hi, unsigned int* fault,
 __device__ __forceinline__ void record_fault(unsigned int* fault, unsigned int bit) {
   if (fault) atomicOr(fault, bit);
 }
+
+// ---------------------------------------------------------------- pad-mask count
+// count[0] = the number of nonzero bytes of mask[0 .. n) (n itself without a mask), by one
+// workgroup of 256 on stream s: integer adds, so any order gives the same. The normaliser of the
+// masked losses of heads.hip (where it is defined) and diffusion_loss.hip. The caller checks the
+// launch (MMT_CHECK_LAUNCH).
+void launch_mask_count(const uint8_t* mask, int64_t n, uint32_t* count, hipStream_t s);
 
 }  // namespace mmt

@@ -16,18 +16,15 @@
 //   dpred = grad_scale A / (K max(sum m, 1)) m d;  dh = (W2^T dpred) [pre > 0];  dP[b] = sum_k dh
 //
 // Launches of the entry: (1) one workgroup counts the mask's ones into scratch[0] (integer adds;
-// B A without a mask); (2) the fused kernel: one wave per sample, four
-// samples per workgroup, the hidden units over the lanes (unit j = lane + 64 u), the loop over the
-// K draws where the sampler loops over its steps; (3) one workgroup adds the B per-sample loss
-// partials (scratch[1 + b]) in ascending order. No float atomics: a sample belongs to one wave,
-// every sum has a fixed order, two calls on the same inputs agree bit for bit.
+// B A without a mask); (2) the fused kernel on the wave-per-sample denoiser core of
+// denoiser_wave.h (its layout, LDS budget and lane reduction), with the loop over the K draws where
+// the sampler loops over its steps; (3) one workgroup adds the B per-sample loss partials
+// (scratch[1 + b]) in ascending order. No float atomics: a sample belongs to one wave, every sum
+// has a fixed order, two calls on the same inputs agree bit for bit.
 //
 // Kernel forms (mmt_diffusion_loss_last_route; MMT_DIFFUSION_LOSS_ROUTE_NONE after a call rejected
-// before its launch): the bf16 W1x rows and W2 columns of all H units sit in LDS, staged once per
-// workgroup as [H][AP] rows (AP = A, or A + 8 when A / 8 is even, so a lane's 16-B pieces land on
-// distinct banks): _LDS while
-//   4 waves * 128 * ceil(H / 64) * 4 B (P[b] and Q[t] / pre of the wave's units) + 4 H AP B <= 160 KB,
-// the sampler's budget; else the same loop reads the weights from global memory (_STREAM).
+// before its launch): _LDS while the weights fit the core's LDS budget (dw::fits_lds), else
+// _STREAM. The Q[t] slots of the wave's LDS rows are reused for the pre-activations.
 //
 // Rounding model: all forward arithmetic is fp32 on exactly widened bf16 weights (as the
 // sampler). The only bf16 roundings are the five backward outputs noisy, h, dh, dpred (rows
@@ -41,29 +38,14 @@
 // 2 k + 1 for eps at the same counters.
 #include <math.h>
 
-#include "common.h"
+#include "denoiser_wave.h"
 
 using namespace mmt;
 
 namespace {
 
-constexpr int DL_NT = 256;     // 4 waves = 4 samples per workgroup
-constexpr int DL_MAXNU = 16;   // H <= 1024
 constexpr int DL_MAXK = 64;
-constexpr int DL_LDS_LIMIT = 160 * 1024;
 
-inline int dl_ap(int A) { return (A / 8) % 2 ? A : A + 8; }
-// dynamic LDS: hp, hq [4][64 nu] fp32, then (LDS form) w1s, w2s [H][AP] bf16
-inline size_t dl_lds_bytes(int A, int H, bool weights) {
-  const size_t hq = (size_t)(DL_NT / 64) * 128 * ((H + 63) / 64) * sizeof(float);
-  return hq + (weights ? (size_t)4 * H * dl_ap(A) : 0);
-}
-
-__device__ __forceinline__ float dl_normal_draw(uint32_t key, uint32_t c) {
-  const float u1 = ((draw_u32(key, 2 * c) >> 8) + 1) * (1.f / 16777216.f);  // (0, 1]
-  const float u2 = (draw_u32(key, 2 * c + 1) >> 8) * (1.f / 16777216.f);
-  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
 // keys of draw k: k = 0 the training streams of mmt_diffusion_prep, k >= 1 layer 0xFFF9
 __device__ __forceinline__ uint32_t dl_t_key(uint32_t seed, uint32_t step, int k) {
   return k == 0 ? stream_key(seed, step, 0xFFFEu, 1) : stream_key(seed, step, 0xFFF9u, 2u * k);
@@ -102,33 +84,15 @@ struct LossArgs {
   unsigned int* fault;
 };
 
-// sum of the mask's n = B A bytes (each counted as 0 / 1; n itself without a mask): integer adds,
-// so any order gives the same
-__global__ __launch_bounds__(DL_NT) void mask_count_kernel(const uint8_t* __restrict__ m, int n,
-                                                           uint32_t* __restrict__ count) {
-  __shared__ uint32_t red[DL_NT / 64];
-  if (!m) {
-    if (threadIdx.x == 0) count[0] = (uint32_t)n;
-    return;
-  }
-  uint32_t s = 0;
-  for (int i = threadIdx.x; i < n; i += DL_NT) s += m[i] != 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) count[0] = red[0] + red[1] + red[2] + red[3];
-}
-
 // loss[0] = A / (K max(count, 1)) * (part[0] + part[1] + ... + part[B-1]), added in that order
-__global__ __launch_bounds__(DL_NT) void loss_sum_kernel(const float* __restrict__ part, int B,
+__global__ __launch_bounds__(dw::NT) void loss_sum_kernel(const float* __restrict__ part, int B,
                                                          float A_over_K,
                                                          const uint32_t* __restrict__ count,
                                                          float* __restrict__ loss) {
-  __shared__ float buf[DL_NT];
+  __shared__ float buf[dw::NT];
   float s = 0.f;
-  for (int b0 = 0; b0 < B; b0 += DL_NT) {
-    const int n = min(DL_NT, B - b0);
+  for (int b0 = 0; b0 < B; b0 += dw::NT) {
+    const int n = min(dw::NT, B - b0);
     if ((int)threadIdx.x < n) buf[threadIdx.x] = part[b0 + threadIdx.x];
     __syncthreads();
     if (threadIdx.x == 0)
@@ -142,42 +106,18 @@ __global__ __launch_bounds__(DL_NT) void loss_sum_kernel(const float* __restrict
 }
 
 template <int A8, bool LDSW>
-__global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossArgs p) {
+__global__ __launch_bounds__(dw::NT) void diffusion_loss_multi_kernel(const LossArgs p) {
   constexpr int A = 8 * A8;
-  constexpr int AP = A8 % 2 ? A : A + 8;
-  extern __shared__ __attribute__((aligned(16))) unsigned char dl_smem[];
   const int H = p.H, nu = (H + 63) / 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* const hp = reinterpret_cast<float*>(dl_smem) + wave * 128 * nu;  // P[b] of my units
-  float* const hq = hp + 64 * nu;  // Q[t] of my units, then their pre-activations
-  const bf16_t* const w1s =
-      reinterpret_cast<const bf16_t*>(dl_smem + (size_t)(DL_NT / 64) * 128 * nu * sizeof(float));
-  const bf16_t* const w2s = w1s + (size_t)H * AP;
-
-  if (LDSW) {  // every wave of the workgroup stages, including those past the batch
-    bf16_t* const d1 = const_cast<bf16_t*>(w1s);
-    bf16_t* const d2 = const_cast<bf16_t*>(w2s);
-    for (int i = threadIdx.x; i < H * A8; i += DL_NT) {
-      const int j = i / A8, c = i - j * A8;
-      *reinterpret_cast<uint4*>(d1 + j * AP + 8 * c) =
-          *reinterpret_cast<const uint4*>(p.w1 + (int64_t)j * p.ld_w1 + 8 * c);
-    }
-    for (int i = threadIdx.x; i < H * A; i += DL_NT) {
-      const int a = i / H, j = i - a * H;
-      d2[j * AP + a] = p.w2[i];  // transposed: unit j's column of W2 as a row
-    }
-    __syncthreads();
-  }
-  const int b = blockIdx.x * (DL_NT / 64) + wave;
+  const dw::Lds s = dw::carve<A8>(H, nu, wave);  // s.hq: Q[t] of my units, then their pre
+  if (LDSW) dw::stage_weights<A8>(s, p.w1, p.ld_w1, p.w2, H);
+  const int b = blockIdx.x * (dw::NT / 64) + wave;
   if (b >= p.B) return;  // wave-uniform, after the only barrier
 
-  // lane l keeps the A8 components a = A8 (l >> 3) + i of the sample's vectors (the 8 lanes of a
-  // group hold copies), where the lane reduction of pred leaves them (sampler.hip)
-  const int grp = lane >> 3, sub = lane & 7;
-  const int a0 = A8 * grp;
   const int64_t gsample = p.sample_offset + b;
-  const int a_draw = a0 + (sub < A8 ? sub : A8 - 1);  // the component this lane draws for its group
-  const uint32_t ctr = (uint32_t)(gsample * A + a_draw);
+  const dw::Lanes<A8> L(lane, gsample);
+  const int sub = L.sub, a0 = L.a0;
   const bool bwd = p.dP != nullptr;
 
   float act[A8], msk[A8], b2r[A8];
@@ -192,14 +132,11 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
   const float norm = (float)A / ((float)p.K * (float)(cnt > 0u ? cnt : 1u));
   const float gscale = p.grad_scale * norm;
 
-  const float* const prow = p.P + (int64_t)b * p.ld_p;
-#pragma unroll
-  for (int u = 0; u < DL_MAXNU; ++u)
-    if (u < nu) hp[64 * u + lane] = prow[min(lane + 64 * u, H - 1)];
+  dw::park_p(s.hp, p.P + (int64_t)b * p.ld_p, H, nu, lane);
 
-  float dp[DL_MAXNU];  // dP[b] of my units, summed over the draws
+  float dp[dw::MAXNU];  // dP[b] of my units, summed over the draws
 #pragma unroll
-  for (int u = 0; u < DL_MAXNU; ++u) dp[u] = 0.f;
+  for (int u = 0; u < dw::MAXNU; ++u) dp[u] = 0.f;
   float loss_acc = 0.f;
 
 #pragma unroll 1
@@ -212,19 +149,11 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
       const uint32_t key = dl_t_key(p.rng[0], p.rng[1], k);
       t = (int)(((uint64_t)draw_u32(key, (uint32_t)gsample) * (uint32_t)p.steps) >> 32);
     }
-    if ((unsigned)t >= (unsigned)p.steps) {  // reported, replaced by row 0, never followed
-      if (lane == 0) record_fault(p.fault, MMT_FAULT_ROW_INDEX);
-      t = 0;
-    }
-    t = __builtin_amdgcn_readfirstlane(t);
-    {  // Q[t] of my units: all loads issued together, then parked (each lane reads back its own)
-      const float* const q = p.Q + (int64_t)t * p.ld_q;
-      float qn[DL_MAXNU];
-#pragma unroll
-      for (int u = 0; u < DL_MAXNU; ++u) qn[u] = q[min(lane + 64 * u, H - 1)];
-#pragma unroll
-      for (int u = 0; u < DL_MAXNU; ++u)
-        if (u < nu) hq[64 * u + lane] = qn[u];
+    t = dw::checked_row(t, p.steps, lane, p.fault);
+    {  // Q[t] of my units: all loads issued together, then parked
+      float qn[dw::MAXNU];
+      dw::load_units(p.Q + (int64_t)t * p.ld_q, H, lane, qn);
+      dw::park_units(s.hq, qn, nu, lane);
     }
 
     float eps[A8], x[A8];
@@ -232,9 +161,7 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
 #pragma unroll
       for (int i = 0; i < A8; ++i) eps[i] = p.eps_in[row * A + a0 + i];
     } else {
-      const float v = dl_normal_draw(dl_eps_key(p.rng[0], p.rng[1], k), ctr);
-#pragma unroll
-      for (int i = 0; i < A8; ++i) eps[i] = __shfl(v, (lane & ~7) | i, 64);
+      L.spread(normal_draw(dl_eps_key(p.rng[0], p.rng[1], k), L.ctr), eps);
     }
     const float ah = p.alpha_hats[t];
     const float c1 = sqrtf(ah), c2 = sqrtf(1.f - ah);
@@ -250,10 +177,7 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
     }
 
     float xb[A];  // noisy as wave-uniform values
-#pragma unroll
-    for (int a = 0; a < A; ++a)
-      xb[a] = __builtin_bit_cast(
-          float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x[a % A8]), 8 * (a / A8)));
+    dw::broadcast<A8>(x, xb);
 
     float e[A];
 #pragma unroll
@@ -263,58 +187,14 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
       const int j = lane + 64 * u;
       const bool live = j < H;
       const int jj = live ? j : H - 1;  // clamped, its hidden value zeroed below
-      float pre = hp[64 * u + lane] + hq[64 * u + lane];
-      const bf16_t* const r1 = LDSW ? w1s + jj * AP : p.w1 + (int64_t)jj * p.ld_w1;
-#pragma unroll
-      for (int c = 0; c < A8; ++c) {
-        const uint4 rowv = *reinterpret_cast<const uint4*>(r1 + 8 * c);
-        const uint32_t rw[4] = {rowv.x, rowv.y, rowv.z, rowv.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          pre = fmaf(xb[8 * c + 2 * q], __uint_as_float(rw[q] << 16), pre);
-          pre = fmaf(xb[8 * c + 2 * q + 1], __uint_as_float(rw[q] & 0xffff0000u), pre);
-        }
-      }
-      hq[64 * u + lane] = pre;  // parked for the backward pass's gate
+      float pre = s.hp[64 * u + lane] + s.hq[64 * u + lane];
+      pre = dw::row_dot<A8>(dw::w1_row<A8, LDSW>(s, p.w1, p.ld_w1, jj), xb, pre);
+      s.hq[64 * u + lane] = pre;  // parked for the backward pass's gate
       const float hv = live ? fmaxf(pre, 0.f) : 0.f;
       if (bwd && live) p.h[row * H + j] = f2bf(hv);
-      if (LDSW) {
-#pragma unroll
-        for (int c = 0; c < A8; ++c) {
-          const uint4 rowv = *reinterpret_cast<const uint4*>(w2s + jj * AP + 8 * c);
-          const uint32_t rw[4] = {rowv.x, rowv.y, rowv.z, rowv.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            e[8 * c + 2 * q] = fmaf(hv, __uint_as_float(rw[q] << 16), e[8 * c + 2 * q]);
-            e[8 * c + 2 * q + 1] =
-                fmaf(hv, __uint_as_float(rw[q] & 0xffff0000u), e[8 * c + 2 * q + 1]);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int a = 0; a < A; ++a) e[a] = fmaf(hv, bf2f(p.w2[(int64_t)a * H + jj]), e[a]);
-      }
+      dw::w2_accumulate<A8, LDSW>(s, p.w2, H, jj, hv, e);
     }
-
-    // sum over the 64 lanes; lane l ends with components A8 (l >> 3) + i (sampler.hip)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const int o = 32 >> s, n = A >> (s + 1);
-      const bool up = (lane & o) != 0;
-#pragma unroll
-      for (int i = 0; i < n; ++i) {
-        float lo = e[i], hi = e[i + n];
-        asm volatile("" : "+v"(lo), "+v"(hi));  // keeps the selects off a lane-varying array index
-        const float send = up ? lo : hi;
-        const float keep = up ? hi : lo;
-        e[i] = keep + __shfl_xor(send, o, 64);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < A8; ++i) {
-#pragma unroll
-      for (int o = 4; o > 0; o >>= 1) e[i] += __shfl_xor(e[i], o, 64);
-    }
+    dw::reduce<A8>(e, lane);
 
     float dpr[A8], lk = 0.f;
 #pragma unroll
@@ -334,10 +214,7 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
       for (int i = 0; i < A8; ++i) p.dpred[row * A + a0 + i] = f2bf(dpr[i]);
     }
     float db[A];  // dpred as wave-uniform values
-#pragma unroll
-    for (int a = 0; a < A; ++a)
-      db[a] = __builtin_bit_cast(
-          float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dpr[a % A8]), 8 * (a / A8)));
+    dw::broadcast<A8>(dpr, db);
     // dh of unit lane + 64 u: its W2 column against dpred, gated by the sign of the parked pre
     auto unit_dh = [&](int u) {
       const int j = lane + 64 * u;
@@ -345,27 +222,18 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
       const int jj = live ? j : H - 1;
       float g = 0.f;
       if (LDSW) {
-#pragma unroll
-        for (int c = 0; c < A8; ++c) {
-          const uint4 rowv = *reinterpret_cast<const uint4*>(w2s + jj * AP + 8 * c);
-          const uint32_t rw[4] = {rowv.x, rowv.y, rowv.z, rowv.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            g = fmaf(db[8 * c + 2 * q], __uint_as_float(rw[q] << 16), g);
-            g = fmaf(db[8 * c + 2 * q + 1], __uint_as_float(rw[q] & 0xffff0000u), g);
-          }
-        }
+        g = dw::row_dot<A8>(dw::w2_row<A8>(s, jj), db, g);
       } else {
 #pragma unroll
         for (int a = 0; a < A; ++a) g = fmaf(db[a], bf2f(p.w2[(int64_t)a * H + jj]), g);
       }
-      g = (live && hq[64 * u + lane] > 0.f) ? g : 0.f;
+      g = (live && s.hq[64 * u + lane] > 0.f) ? g : 0.f;
       if (live) p.dh[row * H + j] = f2bf(g);
       return g;
     };
     if (LDSW) {  // unrolled: dp[u] is a register
 #pragma unroll
-      for (int u = 0; u < DL_MAXNU; ++u)
+      for (int u = 0; u < dw::MAXNU; ++u)
         if (u < nu) dp[u] += unit_dh(u);  // wave-uniform
     } else {
       // streamed weights: a rolled loop (unrolled, the A global loads of all 16 units are hoisted
@@ -374,7 +242,7 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
       for (int u = 0; u < nu; ++u) {
         const float g = unit_dh(u);
 #pragma unroll
-        for (int v = 0; v < DL_MAXNU; ++v) dp[v] += v == u ? g : 0.f;
+        for (int v = 0; v < dw::MAXNU; ++v) dp[v] += v == u ? g : 0.f;
       }
     }
   }
@@ -382,7 +250,7 @@ __global__ __launch_bounds__(DL_NT) void diffusion_loss_multi_kernel(const LossA
   if (lane == 0) p.part[b] = loss_acc;
   if (bwd) {
 #pragma unroll
-    for (int u = 0; u < DL_MAXNU; ++u) {
+    for (int u = 0; u < dw::MAXNU; ++u) {
       const int j = lane + 64 * u;
       if (u < nu && j < H) p.dP[(int64_t)b * H + j] = f2bf(dp[u]);
     }
@@ -438,18 +306,10 @@ __global__ __launch_bounds__(64) void diffusion_loss_dq_kernel(const int32_t* __
 
 int g_loss_route = MMT_DIFFUSION_LOSS_ROUTE_NONE;
 
-template <int A8>
-void launch_loss(bool lds, dim3 grid, size_t smem, hipStream_t s, const LossArgs& p) {
-  if (lds) {
-    static const bool attr_ =
-        (hipFuncSetAttribute((const void*)diffusion_loss_multi_kernel<A8, true>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS_LIMIT), true);
-    (void)attr_;
-    hipLaunchKernelGGL((diffusion_loss_multi_kernel<A8, true>), grid, dim3(DL_NT), smem, s, p);
-  } else {
-    hipLaunchKernelGGL((diffusion_loss_multi_kernel<A8, false>), grid, dim3(DL_NT), smem, s, p);
-  }
-}
+struct LossKernel {
+  template <int A8, bool LDSW>
+  static auto kernel() { return diffusion_loss_multi_kernel<A8, LDSW>; }
+};
 
 }  // namespace
 
@@ -485,27 +345,15 @@ extern "C" int mmt_diffusion_loss_multi(
                 "mmt_diffusion_loss_multi: B * A and K * B must fit an int");
   hipStream_t s = as_stream(stream);
   uint32_t* const count = reinterpret_cast<uint32_t*>(scratch);
-  hipLaunchKernelGGL(mask_count_kernel, dim3(1), dim3(DL_NT), 0, s, pad_mask, B * A, count);
+  launch_mask_count(pad_mask, (int64_t)B * A, count, s);
   MMT_CHECK_LAUNCH("mmt_diffusion_loss_multi");
-  const bool lds = dl_lds_bytes(A, H, true) <= (size_t)DL_LDS_LIMIT;
   LossArgs p{rng, B, K, steps, H, sample_offset, actions, pad_mask, alpha_hats, P, ld_p, Q, ld_q,
              (const bf16_t*)w1, ld_w1, (const bf16_t*)w2, b2, t_in, eps_in, grad_scale, count,
              scratch + 1, t_out, eps_out, (bf16_t*)noisy, (bf16_t*)h, (bf16_t*)dh, (bf16_t*)dpred,
              (bf16_t*)dP, fault_word()};
-  const dim3 grid((B + DL_NT / 64 - 1) / (DL_NT / 64));
-  const size_t smem = dl_lds_bytes(A, H, lds);
-  switch (A / 8) {
-    case 1: launch_loss<1>(lds, grid, smem, s, p); break;
-    case 2: launch_loss<2>(lds, grid, smem, s, p); break;
-    case 3: launch_loss<3>(lds, grid, smem, s, p); break;
-    case 4: launch_loss<4>(lds, grid, smem, s, p); break;
-    case 5: launch_loss<5>(lds, grid, smem, s, p); break;
-    case 6: launch_loss<6>(lds, grid, smem, s, p); break;
-    case 7: launch_loss<7>(lds, grid, smem, s, p); break;
-    default: launch_loss<8>(lds, grid, smem, s, p); break;
-  }
+  const bool lds = dw::dispatch<LossKernel>(A, H, B, s, p);
   MMT_CHECK_LAUNCH("mmt_diffusion_loss_multi");
-  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(DL_NT), 0, s, scratch + 1, B,
+  hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(dw::NT), 0, s, scratch + 1, B,
                      (float)A / (float)K, count, loss);
   MMT_CHECK_LAUNCH("mmt_diffusion_loss_multi");
   g_loss_route = lds ? MMT_DIFFUSION_LOSS_ROUTE_LDS : MMT_DIFFUSION_LOSS_ROUTE_STREAM;

@@ -389,9 +389,7 @@ __global__ void diffusion_prep_kernel(const uint32_t* __restrict__ rng, int B, i
     } else {
       const uint32_t key = stream_key(rng[0], rng[1], 0xFFFEu, 2);
       const uint32_t c = (uint32_t)((sample_offset + b) * A + j);
-      const float u1 = ((draw_u32(key, 2 * c) >> 8) + 1) * (1.f / 16777216.f);  // (0, 1]
-      const float u2 = (draw_u32(key, 2 * c + 1) >> 8) * (1.f / 16777216.f);
-      e = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+      e = normal_draw(key, c);
     }
     eps_out[b * A + j] = e;
     cat[b * ld_cat + j] = f2bf(a1 * actions[b * A + j] + a2 * e);

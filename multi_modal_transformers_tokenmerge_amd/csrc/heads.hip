@@ -29,10 +29,9 @@ constexpr int HD_MAXN = 1024;    // categorical classes
 constexpr int HD_MAXRUN = HD_MAXN / 64;  // classes per lane of the decode scan
 
 // sum of the mask's n bytes (each counted as 0 / 1; n itself without a mask): integer adds, so
-// any order gives the same
-__global__ __launch_bounds__(HD_NT) void head_mask_count_kernel(const uint8_t* __restrict__ m,
-                                                                int64_t n,
-                                                                uint32_t* __restrict__ count) {
+// any order gives the same (launch_mask_count, common.h: the diffusion loss counts with it too)
+__global__ __launch_bounds__(HD_NT) void mask_count_kernel(const uint8_t* __restrict__ m, int64_t n,
+                                                           uint32_t* __restrict__ count) {
   __shared__ uint32_t red[HD_NT / 64];
   if (!m) {
     if (threadIdx.x == 0) count[0] = (uint32_t)n;
@@ -235,6 +234,10 @@ __global__ __launch_bounds__(HD_NT) void head_categorical_decode_kernel(
 
 }  // namespace
 
+void mmt::launch_mask_count(const uint8_t* mask, int64_t n, uint32_t* count, hipStream_t s) {
+  hipLaunchKernelGGL(mask_count_kernel, dim3(1), dim3(HD_NT), 0, s, mask, n, count);
+}
+
 extern "C" int mmt_head_continuous(const float* z, int64_t ldz, int B, int h, int A, const float* y,
                                    const uint8_t* mask, int loss_kind, float max_action,
                                    float* pred, float* scratch, float* loss, void* dz,
@@ -254,8 +257,7 @@ extern "C" int mmt_head_continuous(const float* z, int64_t ldz, int B, int h, in
   hipStream_t s = as_stream(stream);
   uint32_t* const count = reinterpret_cast<uint32_t*>(scratch);
   if (y) {
-    hipLaunchKernelGGL(head_mask_count_kernel, dim3(1), dim3(HD_NT), 0, s, mask, (int64_t)B * W,
-                       count);
+    launch_mask_count(mask, (int64_t)B * W, count, s);
     MMT_CHECK_LAUNCH("mmt_head_continuous");
   }
   const dim3 grid((B + HD_NT / 64 - 1) / (HD_NT / 64));
@@ -287,7 +289,7 @@ extern "C" int mmt_head_categorical(const float* z, int64_t ldz, int R, int N, c
   MMT_CHECK_ARG((int64_t)R * N <= 0x7fffffff, "mmt_head_categorical: R N must fit an int");
   hipStream_t s = as_stream(stream);
   uint32_t* const count = reinterpret_cast<uint32_t*>(scratch);
-  hipLaunchKernelGGL(head_mask_count_kernel, dim3(1), dim3(HD_NT), 0, s, mask, (int64_t)R, count);
+  launch_mask_count(mask, (int64_t)R, count, s);
   MMT_CHECK_LAUNCH("mmt_head_categorical");
   float* const part = scratch + 1;
   hipLaunchKernelGGL(head_categorical_kernel, dim3((R + HD_NT / 64 - 1) / (HD_NT / 64)),

@@ -18,7 +18,7 @@
 // dimension is hard-coded to 8 (:200).
 #include <math.h>
 
-#include "common.h"
+#include "denoiser_wave.h"
 
 using namespace mmt;
 
@@ -65,9 +65,7 @@ __global__ __launch_bounds__(SNT) void diffusion_sample_kernel(
 #pragma unroll
     for (int a = 0; a < SA; ++a) {
       const uint32_t c = (uint32_t)((sample_offset + b) * SA + a);
-      const float u1 = ((draw_u32(key, 2 * c) >> 8) + 1) * (1.f / 16777216.f);  // (0, 1]
-      const float u2 = (draw_u32(key, 2 * c + 1) >> 8) * (1.f / 16777216.f);
-      z[a] = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+      z[a] = normal_draw(key, c);
     }
   }
 #pragma unroll
@@ -116,37 +114,12 @@ __global__ __launch_bounds__(SNT) void diffusion_sample_kernel(
 
 // ---------------------------------------------------------------- step-table sampler
 // mmt_diffusion_sample_steps: K table rows x <- clip(a x + b eps_hat(x, t) + c n) in one launch,
-// for any action width A = 8 .. 64. Still one wave per sample with the hidden units over the
-// lanes, but nothing per-unit lives in registers (2 NU A weights would not fit): the bf16 W1x rows
-// and W2 columns of all H units sit in LDS, staged once per workgroup as [H][AP] rows (AP = A, or
-// A + 8 when A / 8 is even, so a lane's 16-B pieces land on distinct banks), and each lane reads
-// the rows of its unit as 16-B vectors. When they do not fit (STEPS_LDS_LIMIT) the same loop reads
-// them from global memory, where L2 holds them (256 KB at A = 64, H = 1024).
+// for any action width A = 8 .. 64, on the wave-per-sample denoiser core of denoiser_wave.h (the
+// layout, the LDS and the streamed form of the weights, the lane reduction): lane l keeps its A8
+// components of x, z and the step noise. What is written here is the walk over the table.
 //
 // Rounding model: fp32 operands throughout. The weights are the bf16 shadow, widened exactly;
 // x, the hidden layer and every accumulation are fp32 (nothing is rounded to bf16).
-//
-// Sample state: with A8 = A / 8, lane l keeps the A8 components a = A8 (l >> 3) + i, i < A8, of
-// x, z and the step noise (the 8 lanes of a group hold copies). That is where the reduction of
-// the A per-lane partial sums of eps_hat leaves them: three exchange stages (lane bits 5, 4, 3),
-// each halving the vector a lane carries, then three butterflies on the A8 survivors: 5A/4
-// exchanges, not 6A. The matvec takes x[a] as a wave-uniform value (readlane from lane 8 (a / A8)).
-constexpr int ST_NT = 256;                 // 4 waves = 4 samples per workgroup
-constexpr int ST_MAXNU = 16;               // H <= 1024
-constexpr int STEPS_LDS_LIMIT = 160 * 1024;
-
-inline int steps_ap(int A) { return (A / 8) % 2 ? A : A + 8; }
-// dynamic LDS of the step kernel: hp, hq [4][64 nu] fp32, then (LDS form) w1s, w2s [H][AP] bf16
-inline size_t steps_lds_bytes(int A, int H, bool weights) {
-  const size_t hq = (size_t)(ST_NT / 64) * 128 * ((H + 63) / 64) * sizeof(float);
-  return hq + (weights ? (size_t)4 * H * steps_ap(A) : 0);
-}
-
-__device__ __forceinline__ float normal_draw(uint32_t key, uint32_t c) {
-  const float u1 = ((draw_u32(key, 2 * c) >> 8) + 1) * (1.f / 16777216.f);  // (0, 1]
-  const float u2 = (draw_u32(key, 2 * c + 1) >> 8) * (1.f / 16777216.f);
-  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
 
 // Key of step k's noise stream. stream_key keeps 8 bits of its site, so k is split: the site
 // carries 16 + k % 240 (16 .. 255: clear of the head's sites 1 .. 3, the training draws and z) and
@@ -181,50 +154,25 @@ struct StepArgs {
 };
 
 template <int A8, bool LDSW>
-__global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const StepArgs p) {
+__global__ __launch_bounds__(dw::NT) void diffusion_sample_steps_kernel(const StepArgs p) {
   constexpr int A = 8 * A8;
-  constexpr int AP = A8 % 2 ? A : A + 8;
-  extern __shared__ __attribute__((aligned(16))) unsigned char st_smem[];
   const int H = p.H, nu = (H + 63) / 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* const hp = reinterpret_cast<float*>(st_smem) + wave * 128 * nu;  // P[b] of my units
-  float* const hq = hp + 64 * nu;                                         // Q[t_k] of my units
-  const bf16_t* const w1s =
-      reinterpret_cast<const bf16_t*>(st_smem + (size_t)(ST_NT / 64) * 128 * nu * sizeof(float));
-  const bf16_t* const w2s = w1s + (size_t)H * AP;
-
-  if (LDSW) {  // every wave of the workgroup stages, including those past the batch
-    bf16_t* const d1 = const_cast<bf16_t*>(w1s);
-    bf16_t* const d2 = const_cast<bf16_t*>(w2s);
-    for (int i = threadIdx.x; i < H * A8; i += ST_NT) {
-      const int j = i / A8, c = i - j * A8;
-      *reinterpret_cast<uint4*>(d1 + j * AP + 8 * c) =
-          *reinterpret_cast<const uint4*>(p.w1 + (int64_t)j * p.ld_w1 + 8 * c);
-    }
-    for (int i = threadIdx.x; i < H * A; i += ST_NT) {
-      const int a = i / H, j = i - a * H;
-      d2[j * AP + a] = p.w2[i];  // transposed: unit j's column of W2 as a row
-    }
-    __syncthreads();
-  }
-  const int b = blockIdx.x * (ST_NT / 64) + wave;
+  const dw::Lds s = dw::carve<A8>(H, nu, wave);
+  if (LDSW) dw::stage_weights<A8>(s, p.w1, p.ld_w1, p.w2, H);
+  const int b = blockIdx.x * (dw::NT / 64) + wave;
   if (b >= p.B) return;  // wave-uniform, after the only barrier
 
-  const int grp = lane >> 3, sub = lane & 7;
-  const int a0 = A8 * grp;  // first action component this lane keeps
+  const dw::Lanes<A8> L(lane, p.sample_offset + b);
+  const int sub = L.sub, a0 = L.a0;
   const bool fresh = (p.flags & MMT_SAMPLE_FRESH_NOISE) != 0;
-  const int64_t gsample = p.sample_offset + b;
-  const int a_draw = a0 + (sub < A8 ? sub : A8 - 1);  // the component this lane draws for its group
-  const uint32_t ctr = (uint32_t)(gsample * A + a_draw);
 
   float x[A8], z[A8], nz[A8], b2r[A8];
   if (p.z_in) {
 #pragma unroll
     for (int i = 0; i < A8; ++i) z[i] = p.z_in[(int64_t)b * A + a0 + i];
   } else {
-    const float v = normal_draw(stream_key(p.rng[0], p.rng[1], 0xFFFEu, 3), ctr);
-#pragma unroll
-    for (int i = 0; i < A8; ++i) z[i] = __shfl(v, (lane & ~7) | i, 64);
+    L.spread(normal_draw(stream_key(p.rng[0], p.rng[1], 0xFFFEu, 3), L.ctr), z);
   }
 #pragma unroll
   for (int i = 0; i < A8; ++i) {
@@ -237,46 +185,33 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const Ste
     for (int i = 0; i < A8; ++i) p.z_out[(int64_t)b * A + a0 + i] = z[i];
   }
 
-  // P[b] of this lane's units is parked in LDS once, Q[t_k] every step (each lane reads back only
-  // what it wrote, so no barrier): the unit loop can then index them. The Q row, the table row
+  // P[b] of this lane's units is parked in LDS once, Q[t_k] every step. The Q row, the table row
   // and the step index after it are fetched a step ahead with plain unconditional loads (clamped
   // addresses, nothing computed on them before the next step), so no step waits on memory. All
-  // ST_MAXNU loads are issued whatever nu is: those past nu re-read Q[t][H-1], one cached word
-  // for the whole wave, and a `u < nu` guard costs more than it saves, because each guarded
-  // block ends in a wait for its own loads (32 steps at H = 384, launch alone: 46.7 us as here,
-  // 53.8 us with a guard per unit, 48.9 us with one per four units, at A = 8; 112.5 / 120.0 /
-  // 114.3 us at A = 32).
-  const float* const prow = p.P + (int64_t)b * p.ld_p;
-#pragma unroll
-  for (int u = 0; u < ST_MAXNU; ++u)
-    if (u < nu) hp[64 * u + lane] = prow[min(lane + 64 * u, H - 1)];
-  auto checked_t = [&](int t) {
-    if ((unsigned)t >= (unsigned)p.q_rows) {
-      if (lane == 0) record_fault(p.fault, MMT_FAULT_ROW_INDEX);
-      t = 0;
-    }
-    return __builtin_amdgcn_readfirstlane(t);
-  };
-  float qn[ST_MAXNU];
-  auto load_q = [&](int t) {
-    const float* const q = p.Q + (int64_t)t * p.ld_q;
-#pragma unroll
-    for (int u = 0; u < ST_MAXNU; ++u) qn[u] = q[min(lane + 64 * u, H - 1)];
+  // MAXNU loads are issued whatever nu is: a `u < nu` guard costs more than it saves, because
+  // each guarded block ends in a wait for its own loads (32 steps at H = 384, launch alone:
+  // 46.7 us as here, 53.8 us with a guard per unit, 48.9 us with one per four units, at A = 8;
+  // 112.5 / 120.0 / 114.3 us at A = 32).
+  dw::park_p(s.hp, p.P + (int64_t)b * p.ld_p, H, nu, lane);
+  float qn[dw::MAXNU];
+  auto load_q = [&](int t) {  // t raw: checked when its Q row is fetched
+    t = dw::checked_row(t, p.q_rows, lane, p.fault);
+    dw::load_units(p.Q + (int64_t)t * p.ld_q, H, lane, qn);
   };
   const int last = p.n_steps - 1;
-  load_q(checked_t(p.step_t[0]));
-  int t_next = p.step_t[min(1, last)];  // raw: checked when its Q row is fetched
+  load_q(p.step_t[0]);
+  int t_next = p.step_t[min(1, last)];
   float can = p.step_coef[0], cbn = p.step_coef[1], ccn = p.step_coef[2];
 
 #pragma unroll 1
   for (int k = 0; k < p.n_steps; ++k) {
 #pragma unroll
-    for (int u = 0; u < ST_MAXNU; ++u)
-      if (u < nu) hq[64 * u + lane] = qn[u];
+    for (int u = 0; u < dw::MAXNU; ++u)
+      if (u < nu) s.hq[64 * u + lane] = qn[u];
     const float ca = can, cb = cbn, cc = ccn;
     {  // step k + 1's operands (the last step refetches its own)
       const int kn = min(k + 1, last);
-      load_q(checked_t(t_next));
+      load_q(t_next);
       t_next = p.step_t[min(k + 2, last)];
       can = p.step_coef[3 * kn];
       cbn = p.step_coef[3 * kn + 1];
@@ -288,9 +223,7 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const Ste
 #pragma unroll
         for (int i = 0; i < A8; ++i) nz[i] = p.noise_in[((int64_t)k * p.B + b) * A + a0 + i];
       } else {
-        const float v = normal_draw(step_noise_key(p.rng[0], p.rng[1], k), ctr);
-#pragma unroll
-        for (int i = 0; i < A8; ++i) nz[i] = __shfl(v, (lane & ~7) | i, 64);
+        L.spread(normal_draw(step_noise_key(p.rng[0], p.rng[1], k), L.ctr), nz);
       }
       if (p.noise_out && sub == 0) {
 #pragma unroll
@@ -299,10 +232,7 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const Ste
     }
 
     float xb[A];  // x as wave-uniform values
-#pragma unroll
-    for (int a = 0; a < A; ++a)
-      xb[a] = __builtin_bit_cast(
-          float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x[a % A8]), 8 * (a / A8)));
+    dw::broadcast<A8>(x, xb);
 
     float e[A];
 #pragma unroll
@@ -312,52 +242,21 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const Ste
       const int j = lane + 64 * u;
       const bool live = j < H;
       const int jj = live ? j : H - 1;  // clamped, its hidden value zeroed below
-      float h = hp[64 * u + lane] + hq[64 * u + lane];
-      const bf16_t* const r1 = LDSW ? w1s + jj * AP : p.w1 + (int64_t)jj * p.ld_w1;
-#pragma unroll
-      for (int c = 0; c < A8; ++c) {
-        const uint4 row = *reinterpret_cast<const uint4*>(r1 + 8 * c);
-        const uint32_t rw[4] = {row.x, row.y, row.z, row.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          h = fmaf(xb[8 * c + 2 * q], __uint_as_float(rw[q] << 16), h);
-          h = fmaf(xb[8 * c + 2 * q + 1], __uint_as_float(rw[q] & 0xffff0000u), h);
-        }
-      }
+      float h = s.hp[64 * u + lane] + s.hq[64 * u + lane];
+      h = dw::row_dot<A8>(dw::w1_row<A8, LDSW>(s, p.w1, p.ld_w1, jj), xb, h);
       h = live ? fmaxf(h, 0.f) : 0.f;
-      if (LDSW) {
-#pragma unroll
-        for (int c = 0; c < A8; ++c) {
-          const uint4 row = *reinterpret_cast<const uint4*>(w2s + jj * AP + 8 * c);
-          const uint32_t rw[4] = {row.x, row.y, row.z, row.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            e[8 * c + 2 * q] = fmaf(h, __uint_as_float(rw[q] << 16), e[8 * c + 2 * q]);
-            e[8 * c + 2 * q + 1] =
-                fmaf(h, __uint_as_float(rw[q] & 0xffff0000u), e[8 * c + 2 * q + 1]);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int a = 0; a < A; ++a) e[a] = fmaf(h, bf2f(p.w2[(int64_t)a * H + jj]), e[a]);
-      }
+      dw::w2_accumulate<A8, LDSW>(s, p.w2, H, jj, h, e);
     }
-
-    // sum over the 64 lanes; lane l ends with components A8 (l >> 3) + i
+    // dw::reduce, written out, and the park of qn above not through dw::park_units: through the
+    // helpers this kernel is scheduled with one more full vmcnt / lgkmcnt wait per step (launch
+    // alone, 32 steps, H = 384, B = 1 / 64 / 512: 47.9 / 50.7 / 51.1 us against 47.2 / 49.6 /
+    // 50.0 us as here at A = 8; 113.7 / 118.0 / 119.7 against 112.1 / 116.0 / 117.8 us at A = 32)
 #pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      const int o = 32 >> s, n = A >> (s + 1);
+    for (int st = 0; st < 3; ++st) {
+      const int o = 32 >> st, n = A >> (st + 1);
       const bool up = (lane & o) != 0;
 #pragma unroll
-      for (int i = 0; i < n; ++i) {
-        float lo = e[i], hi = e[i + n];
-        // opaque to the optimiser: it otherwise folds the two selects into e[i + (up ? 0 : n)], a
-        // lane-varying index into the register array (a compare-select chain over all of e)
-        asm volatile("" : "+v"(lo), "+v"(hi));
-        const float send = up ? lo : hi;
-        const float keep = up ? hi : lo;
-        e[i] = keep + __shfl_xor(send, o, 64);
-      }
+      for (int i = 0; i < n; ++i) e[i] = dw::exchange(e[i], e[i + n], up, o);
     }
 #pragma unroll
     for (int i = 0; i < A8; ++i) {
@@ -381,11 +280,11 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_steps_kernel(const Ste
 
 // MMT_SAMPLE_DRAWS_ONLY: z and the step noise a full call would use, one thread per (b, a), with
 // the sampler kernel's own draw (same keys, counters and arithmetic) and nothing else.
-__global__ __launch_bounds__(ST_NT) void diffusion_sample_draws_kernel(
+__global__ __launch_bounds__(dw::NT) void diffusion_sample_draws_kernel(
     const uint32_t* __restrict__ rng, int B, int A, int n_steps, int64_t sample_offset,
     bool fresh, const float* __restrict__ z_in, const float* __restrict__ noise_in,
     float* __restrict__ z_out, float* __restrict__ noise_out) {
-  const int idx = blockIdx.x * ST_NT + threadIdx.x;  // b * A + a
+  const int idx = blockIdx.x * dw::NT + threadIdx.x;  // b * A + a
   if (idx >= B * A) return;
   const uint32_t ctr = (uint32_t)(sample_offset * A + idx);
   if (z_out)
@@ -399,18 +298,10 @@ __global__ __launch_bounds__(ST_NT) void diffusion_sample_draws_kernel(
 
 int g_sampler_route = MMT_SAMPLER_ROUTE_NONE;
 
-template <int A8>
-void launch_steps(bool lds, dim3 grid, size_t smem, hipStream_t s, const StepArgs& p) {
-  if (lds) {
-    static const bool attr_ =
-        (hipFuncSetAttribute((const void*)diffusion_sample_steps_kernel<A8, true>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, STEPS_LDS_LIMIT), true);
-    (void)attr_;
-    hipLaunchKernelGGL((diffusion_sample_steps_kernel<A8, true>), grid, dim3(ST_NT), smem, s, p);
-  } else {
-    hipLaunchKernelGGL((diffusion_sample_steps_kernel<A8, false>), grid, dim3(ST_NT), smem, s, p);
-  }
-}
+struct StepKernel {
+  template <int A8, bool LDSW>
+  static auto kernel() { return diffusion_sample_steps_kernel<A8, LDSW>; }
+};
 
 }  // namespace
 
@@ -444,8 +335,8 @@ extern "C" int mmt_diffusion_sample_steps(const uint32_t* rng, int B, int A, int
                   "mmt_diffusion_sample_steps: MMT_SAMPLE_DRAWS_ONLY needs z_out or noise_out");
     MMT_CHECK_ARG((int64_t)B * A <= 0x7fffffff,
                   "mmt_diffusion_sample_steps: MMT_SAMPLE_DRAWS_ONLY needs B * A to fit an int");
-    hipLaunchKernelGGL(diffusion_sample_draws_kernel, dim3((B * A + ST_NT - 1) / ST_NT),
-                       dim3(ST_NT), 0, s, rng, B, A, n_steps, sample_offset, fresh, z_in, noise_in,
+    hipLaunchKernelGGL(diffusion_sample_draws_kernel, dim3((B * A + dw::NT - 1) / dw::NT),
+                       dim3(dw::NT), 0, s, rng, B, A, n_steps, sample_offset, fresh, z_in, noise_in,
                        z_out, noise_out);
     MMT_CHECK_LAUNCH("mmt_diffusion_sample_steps");
     g_sampler_route = MMT_SAMPLER_ROUTE_STEPS_DRAWS;
@@ -460,22 +351,10 @@ extern "C" int mmt_diffusion_sample_steps(const uint32_t* rng, int B, int A, int
   MMT_CHECK_ARG(ld_p >= H && ld_q >= H && ld_w1 >= A, "mmt_diffusion_sample_steps: leading dims");
   MMT_CHECK_ARG(ld_w1 % 8 == 0 && ((uintptr_t)w1 & 15) == 0 && ((uintptr_t)w2 & 15) == 0,
                 "mmt_diffusion_sample_steps: W1 rows and W2 must start on 16-B boundaries");
-  const bool lds = steps_lds_bytes(A, H, true) <= (size_t)STEPS_LDS_LIMIT;
   StepArgs p{rng, B, n_steps, q_rows, H, flags, sample_offset, P, ld_p, Q, ld_q,
              (const bf16_t*)w1, ld_w1, (const bf16_t*)w2, b2, step_t, step_coef, clip, z_in,
              noise_in, actions, z_out, noise_out, fault_word()};
-  const dim3 grid((B + ST_NT / 64 - 1) / (ST_NT / 64));
-  const size_t smem = steps_lds_bytes(A, H, lds);
-  switch (A / 8) {
-    case 1: launch_steps<1>(lds, grid, smem, s, p); break;
-    case 2: launch_steps<2>(lds, grid, smem, s, p); break;
-    case 3: launch_steps<3>(lds, grid, smem, s, p); break;
-    case 4: launch_steps<4>(lds, grid, smem, s, p); break;
-    case 5: launch_steps<5>(lds, grid, smem, s, p); break;
-    case 6: launch_steps<6>(lds, grid, smem, s, p); break;
-    case 7: launch_steps<7>(lds, grid, smem, s, p); break;
-    default: launch_steps<8>(lds, grid, smem, s, p); break;
-  }
+  const bool lds = dw::dispatch<StepKernel>(A, H, B, s, p);
   MMT_CHECK_LAUNCH("mmt_diffusion_sample_steps");
   g_sampler_route = lds ? MMT_SAMPLER_ROUTE_STEPS_LDS : MMT_SAMPLER_ROUTE_STEPS_STREAM;
   return MMT_OK;
