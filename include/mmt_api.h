@@ -48,13 +48,15 @@ int mmt_version(void);
 /* Device-side index checks. The entry points that address memory through caller-supplied index
  * arrays (mmt_tome_merge_wavg_fwd / _bwd, mmt_tome_merge_seqnorm_fwd, mmt_ln_unmerge_dropout_bwd,
  * mmt_gather_rows, mmt_topk_scatter_bwd, mmt_tome_pos_map, mmt_tome_source_step / _groups,
- * mmt_tome_unmerge_fwd / _bwd) cannot see those device values at launch. Their kernels
+ * mmt_tome_unmerge_fwd / _bwd, mmt_value_tokens_fwd / _bwd) cannot see those device values at
+ * launch. Their kernels
  * range-check every index they use; an invalid one is replaced by 0 (so no access leaves its
  * tensor and the context survives) and sets a bit of a library-wide device status word:
  *   MMT_FAULT_TOME_INDEX     unm / src not in [0, ceil(t/2)), dst not in [0, t/2)
  *   MMT_FAULT_TOME_PARTITION unm and src repeat an a-token (not a partition of the a half)
  *   MMT_FAULT_POS_MAP        pos_map entry not in [0, t - r)
- *   MMT_FAULT_ROW_INDEX      gathered / scattered row not in [0, L)
+ *   MMT_FAULT_ROW_INDEX      gathered / scattered row not in [0, L); a saved value token not in
+ *                            [0, num_bins) (mmt_value_tokens_bwd: the entry is skipped)
  * mmt_device_status synchronises `stream`, returns MMT_OK if the word is clear, else clears it and
  * returns MMT_ERR_INVALID with the decoded bits in mmt_last_error(). Not graph-capturable (it
  * synchronises); call it after a step, a test or a bench. The reference's jnp gathers cannot fault
@@ -660,7 +662,8 @@ int mmt_patch_positions(const uint32_t* rng, uint32_t site, int B, int I, int Hi
 
 /* ------------------------------------------------------------------ sequence assembly
  * x0[b, l] = source(l) + pe[l] with source = text[b, j] | img[b, j] + row_emb[rtok] + col_emb[ctok]
- * | readout_pe[j]  (row_src[l] = kind << 24 | j, kind 0 text / 1 image / 2 readout):
+ * | readout_pe[j]  (row_src[l] = kind << 24 | j, kind 0 text / 1 image / 2 readout; a row of
+ * kind 3, a value token, is left untouched by both directions: mmt_value_tokens_fwd / _bwd):
  * TokenSequence.assemble_embeddings (token_sequencer.py:255-269), readout AddPositionEmbedding
  * on zeros (readout.py:18-33, octo.py:103-108), ImageTokenizer embeddings (:300-307) and the
  * encoder's learned position embedding (attention.py:71-85,97-100), fused. fp32 tables.
@@ -703,6 +706,48 @@ int mmt_rows_mean_fwd(const void* x, int64_t xs_b, int64_t xs_t, int B, int D,
  * in the rows with row_flag[l] >= 0, 0 in every other row (de bf16, row stride ld_de). */
 int mmt_rows_mean_bwd(const void* de, int64_t ld_de, int B, int L, int D, const int32_t* row_flag,
                       int nrows, void* dx, mmt_stream_t stream);
+
+/* ------------------------------------------------------------------ value tokens
+ * Low-dimensional numbers (proprioception: joint angles, gripper opening, end-effector pose, the
+ * previous action) as sequence rows (csrc/values.hip): the reference's Gato-style pieces,
+ * tokenizers/numeric_values/value_tokenizer.py:18-34: mu_law_encoder companding (:33-34), uniform
+ * bins, one nn.Embed table over the discrete ids (ActionTokenizer, :18-30). Values are expected
+ * normalised to [-1, 1]. For a value v, N = num_bins, all in fp32:
+ *   s = fminf(fmaxf(v, -1), 1)                       clamp; IEEE fmax / fmin send NaN to -1
+ *   y = s                                            MMT_VALUE_UNIFORM
+ *   y = copysign(log1pf(mu |s|) / log1pf(mu), s)     MMT_VALUE_MU_LAW
+ *   token = min(N - 1, (int)floorf((y + 1) * 0.5f * N))
+ * so -1, -inf and NaN give token 0, 0 gives N / 2, and 1, +inf and anything above 1 give N - 1.
+ * The row of value j of sample b: x0[b, rows[j], :] = table[token(b, j), :] + pe[rows[j], :], one
+ * fp32 add (bit-exact). table (N, D) fp32 is shared by every value; pe (the encoder's learned
+ * position embedding, one row per sequence position) tells the slots apart.
+ *
+ * Forward. values fp32 (B, n) with row stride ld_v >= n; rows (n,) int32, the sequence row of each
+ * value; x0 fp32 with element strides xs_b, xs_t. Writes tok (B, n) int32 (kept for the backward)
+ * and the n rows of x0 per sample as 16-B vectors, no other row (mmt_seq_assemble_fwd skips the
+ * rows of kind 3, which these are). Checked before the launch (MMT_ERR_INVALID): null pointers;
+ * B, n <= 0; D <= 0 or D % 8 != 0; num_bins outside MMT_VALUE_MIN_BINS .. MMT_VALUE_MAX_BINS; an
+ * unknown encoding; mu <= 0 or not finite (mu-law only); x0 or table not 16-B aligned; xs_t < D;
+ * xs_b or xs_t not a multiple of 4. A row outside its sample (rows[j] < 0 or rows[j] * xs_t + D >
+ * xs_b) is not written: MMT_FAULT_ROW_INDEX. */
+enum { MMT_VALUE_UNIFORM = 0, MMT_VALUE_MU_LAW = 1 };
+#define MMT_VALUE_MIN_BINS 2
+#define MMT_VALUE_MAX_BINS 4096
+int mmt_value_tokens_fwd(const float* values, int64_t ld_v, int B, int n, int encoding, float mu,
+                         int num_bins, const float* table, const float* pe, const int32_t* rows,
+                         int D, void* x0, int64_t xs_b, int64_t xs_t, int32_t* tok,
+                         mmt_stream_t stream);
+/* Backward: dtable[k, :] += sum of dx0[b, rows[j], :] over the tokens tok[b, j] == k. The sum is
+ * formed in ONE fp32 accumulator per table entry in ascending (b, j) order and then added once to
+ * dtable (which holds zero after zero_grad): each entry has one writer and a fixed order, so there
+ * are no float atomics, the result is bitwise reproducible with and without the deterministic
+ * mode, and it equals a sequential fp32 sum in that order bit for bit. d(pe) is mmt_colsum over
+ * dx0, as for every other row; no gradient reaches the values. dx0 fp32, strides as above. The
+ * same checks as the forward (dx0 and dtable 16-B aligned). A tok entry outside [0, num_bins) or a
+ * row outside its sample is skipped: MMT_FAULT_ROW_INDEX. */
+int mmt_value_tokens_bwd(const void* dx0, int64_t xs_b, int64_t xs_t, int B, int n,
+                         const int32_t* tok, const int32_t* rows, int D, int num_bins,
+                         float* dtable, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ attention pooling
  * MultiHeadAttentionPooling (attention_blocks/attention.py:122-150) of the readout tokens, the

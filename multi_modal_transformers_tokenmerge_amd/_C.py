@@ -85,6 +85,8 @@ SIGNATURES: dict[str, list] = {
     "mmt_patch_positions": [P, U32, I, I, I, I, I, I, L, P, P, P],
     "mmt_seq_assemble_fwd": [I, I, I, P, P, I, P, I, P, P, P, P, P, P, P, P],
     "mmt_seq_assemble_bwd": [I, I, I, P, P, P, I, P, I, P, P, P, I, P, P, P, P],
+    "mmt_value_tokens_fwd": [P, L, I, I, I, F, I, P, P, P, I, P, L, L, P, P],
+    "mmt_value_tokens_bwd": [P, L, L, I, I, P, P, I, I, P, P],
     "mmt_patch_embed_grad": [I, I, I, I, I, I, I, P, P, P, P, P, P, P],
     "mmt_stem_conv_pool": [P, I, I, I, P, P, P, P, P],
     "mmt_stem_conv_wgrad_slabs": [I, I, I],
@@ -311,6 +313,8 @@ def diffusion_loss_last_route() -> int:
     return call("mmt_diffusion_loss_last_route")
 
 
+VALUE_UNIFORM, VALUE_MU_LAW = 0, 1   # MMT_VALUE_* (mmt_value_tokens_fwd encoding)
+VALUE_MIN_BINS, VALUE_MAX_BINS = 2, 4096
 HEAD_LOSS_MSE, HEAD_LOSS_L1 = 0, 1   # MMT_HEAD_LOSS_* (mmt_head_continuous loss_kind)
 DECODE_ARGMAX, DECODE_SAMPLE = 0, 1  # MMT_DECODE_* (mmt_head_categorical_decode mode)
 

@@ -1110,3 +1110,58 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean, rstd, gamma, addend=N
             addend.stride(0) if addend is not None else 0, ptr(out), out.stride(0), ptr(dyxhat),
             _C.stream_ptr())
     return out, dyxhat
+
+
+# ------------------------------------------------------------------------------------ value tokens
+VALUE_ENCODINGS = {"uniform": _C.VALUE_UNIFORM, "mu_law": _C.VALUE_MU_LAW}
+
+
+def _check_value_rows(x: torch.Tensor, rows: torch.Tensor, what: str):
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError(f"{what} must be fp32 (B, L, D) with unit inner stride")
+    _check_i32(rows, (rows.numel(),), "rows")
+
+
+def value_tokens_fwd(values: torch.Tensor, rows: torch.Tensor, table: torch.Tensor,
+                     pe: torch.Tensor, x0: torch.Tensor, encoding: str = "mu_law",
+                     mu: float = 255.0, tok: torch.Tensor | None = None) -> torch.Tensor:
+    """values (B, n) fp32 (row stride >= n), rows (n,) int32, table (N, D) and pe (L, D) fp32
+    contiguous, x0 (B, L, D) fp32 (strided): writes x0[b, rows[j]] = table[token(b, j)] + pe[rows[j]]
+    and nothing else of x0; returns the (B, n) int32 tokens (mmt_value_tokens_fwd)."""
+    _dev(values, rows, table, pe, x0, tok)
+    _check_value_rows(x0, rows, "x0")
+    B, L, D = x0.shape
+    n = rows.numel()
+    if values.dtype != torch.float32 or tuple(values.shape) != (B, n) or \
+            (n > 1 and values.stride(1) != 1):
+        raise ValueError(f"values must be fp32 {(B, n)} with unit inner stride")
+    if encoding not in VALUE_ENCODINGS:
+        raise ValueError(f"encoding must be one of {sorted(VALUE_ENCODINGS)}, got {encoding!r}")
+    N = table.shape[0]
+    for t, shape, what in ((table, (N, D), "table"), (pe, (L, D), "pe")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous fp32 {shape}")
+    if tok is None:
+        tok = torch.empty((B, n), dtype=torch.int32, device=x0.device)
+    _check_i32(tok, (B, n), "tok")
+    _C.call("mmt_value_tokens_fwd", ptr(values), values.stride(0) if B > 1 else n, B, n,
+            VALUE_ENCODINGS[encoding], float(mu), N, ptr(table), ptr(pe), ptr(rows), D, ptr(x0),
+            x0.stride(0), x0.stride(1), ptr(tok), _C.stream_ptr())
+    return tok
+
+
+def value_tokens_bwd(dx0: torch.Tensor, tok: torch.Tensor, rows: torch.Tensor,
+                     dtable: torch.Tensor) -> torch.Tensor:
+    """dtable (N, D) fp32 += the rows dx0[b, rows[j]] of the tokens tok[b, j] == k, summed in one
+    fp32 accumulator per entry in ascending (b, j) order (mmt_value_tokens_bwd: no atomics)."""
+    _dev(dx0, tok, rows, dtable)
+    _check_value_rows(dx0, rows, "dx0")
+    B, _, D = dx0.shape
+    n = rows.numel()
+    _check_i32(tok, (B, n), "tok")
+    if dtable.dim() != 2 or dtable.dtype != torch.float32 or dtable.shape[1] != D or \
+            not dtable.is_contiguous():
+        raise ValueError(f"dtable must be contiguous fp32 (N, {D})")
+    _C.call("mmt_value_tokens_bwd", ptr(dx0), dx0.stride(0), dx0.stride(1), B, n, ptr(tok),
+            ptr(rows), D, dtable.shape[0], ptr(dtable), _C.stream_ptr())
+    return dtable

@@ -195,6 +195,8 @@ def _rules(model) -> Dict[str, Rule]:
     rules["AddPositionEmbedding_0/pos_embedding"] = (["readout_encoder/pos_embedding"], _lead1, _drop1)
     rules["StackedEncoder1DBlock_0/posembed_input/pos_embedding"] = (
         ["attention_blocks/posembed_input/pos_embedding"], _lead1, _drop1)
+    if getattr(model, "value_tokenizer", None) is not None:  # the nn.Embed of the Value sets
+        rules["ValueTokenizer_0/embedding"] = (["ValueTokenizer_0/embedding"], _ident, _ident)
     if model.text_proj is not None:  # this build's projection of T5 features to D (no reference twin)
         rules["TextProjection_0/kernel"] = (["TextProjection_0/kernel"], _dense_T, _dense_T)
         rules["TextProjection_0/bias"] = (["TextProjection_0/bias"], _ident, _ident)

@@ -23,7 +23,8 @@ which are not available on the GPU box.
   ``action_heads.n_diffusion_samples`` (independent (t, eps) draws per sample in its loss) and
   ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``action_heads.pred_horizon``
   (the chunk length of the continuous and categorical heads) and
-  ``action_heads.continuous_loss`` ("mse" | "l1"), ``fp8_matmul``,
+  ``action_heads.continuous_loss`` ("mse" | "l1"), ``tokenizers.values.encoder`` (the
+  ValueTokenizer node behind the ``Value{n}`` sets of the sequence), ``fp8_matmul``,
   ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
@@ -160,6 +161,7 @@ TARGETS = {
     _REF + "tokenizers.images.image_tokenizer.ImageTokenizer": _BUILD + "tokenizers.images.image_tokenizer.ImageTokenizer",
     _REF + "tokenizers.images.image_tokenizer.ResNetV2Block": _BUILD + "tokenizers.images.image_tokenizer.ResNetV2Block",
     _REF + "tokenizers.text.t5_base.T5Tokenizer": _BUILD + "tokenizers.text.t5_base.T5Tokenizer",
+    _REF + "tokenizers.numeric_values.value_tokenizer.ValueTokenizer": _BUILD + "tokenizers.numeric_values.value_tokenizer.ValueTokenizer",
     _REF + "action_heads.diffusion.DiffusionActionHead": _BUILD + "action_heads.diffusion.DiffusionActionHead",
     _REF + "action_heads.continuous.ContinuousActionHead": _BUILD + "action_heads.continuous.ContinuousActionHead",
     _REF + "action_heads.categorical.CategoricalActionHead": _BUILD + "action_heads.categorical.CategoricalActionHead",
@@ -303,6 +305,10 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     kw["continuous_loss"] = str(heads_cfg.get("continuous_loss", "mse"))
     sampler = heads_cfg.get("sampler")
     kw["sampler"] = None if sampler is None else dict(sampler)
+    # the value tokenizer of the Value{n} sets: the _target_ node's own fields
+    vt = _first(cfg, "tokenizers.values.encoder", default=None)
+    if vt is not None:
+        kw["value_tokenizer"] = {k: vt[k] for k in ("num_bins", "mu", "encoding") if k in vt}
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

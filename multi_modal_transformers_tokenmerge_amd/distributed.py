@@ -97,11 +97,18 @@ class DDPStep:
     # (or after reset_text()) encodes the step's own `txt` before it starts, so a loader may
     # write the first batch after build(); from then on `txt` is not read for the encoder — each
     # step's text arrives through txt_next one call earlier (write both buffers, one batch apart).
+    #
+    # values: the numbers behind the model's Value sets (Octo.generate_readouts), a static device
+    # buffer read by every replay like img and act; required with Value sets, refused without.
 
     def __init__(self, model, state, txt, img, act, reducer: GradAllReducer | None = None,
-                 stages="auto", use_graph: bool = True, txt_next=None):
+                 stages="auto", use_graph: bool = True, txt_next=None, values=None):
         self.model, self.state = model, state
         self.txt, self.img, self.act = txt, img, act
+        if values is not None or model.n_values:    # ValueError now, not inside a capture
+            model._check_values(values, img.shape[0])
+        self.values = values
+        self._vkw = {} if values is None else {"values": values}
         self.t5_pf = (txt_next is not None and txt is not None
                       and getattr(model, "t5", None) is not None)
         self.txt_next = txt_next
@@ -115,6 +122,11 @@ class DDPStep:
         self.bounds = model.stage_bounds(stages) if self.distributed else [model.cfg.num_blocks, 0]
         self.S = len(self.bounds) - 1
         self.regions = model.grad_regions(self.bounds) if self.S > 1 else None
+        # the value tokenizer's embedding gradient (Octo.tail_region): declared after the heads
+        # but final only after the last stage, so the staged form reduces it there
+        self.tail = model.tail_region() if self.S > 1 else None
+        if self.tail is not None and not model.store.region_trainable(*self.tail):
+            self.tail = None
         self.use_graph = use_graph
         if self.distributed and getattr(state.allreduce, "grad_scale", 1.0) != reducer.grad_scale:
             # the 1/N average lives in AdamW's grad_scale (state.allreduce): a reducer given only
@@ -176,7 +188,8 @@ class DDPStep:
         if early:
             self._t5_fork()
         loss, st = m.compute_diffusion_denoise_loss(self.txt, self.img, self.act, True, s.rng,
-                                                    s.sample_offset, t5_out=self.t5_cur)
+                                                    s.sample_offset, t5_out=self.t5_cur,
+                                                    **self._vkw)
         if self._t5_graphed_in and not early:
             self._t5_fork()
         m.backward(st)
@@ -208,7 +221,8 @@ class DDPStep:
             if early:
                 self._t5_fork()
             loss, st = m.compute_diffusion_denoise_loss(self.txt, self.img, self.act, True, s.rng,
-                                                        s.sample_offset, t5_out=self.t5_cur)
+                                                        s.sample_offset, t5_out=self.t5_cur,
+                                                        **self._vkw)
             self.loss_buf.copy_(loss)
             self._st["st"] = st
             if self._t5_graphed_in and not early:
@@ -252,13 +266,14 @@ class DDPStep:
             return 0
         if not self.regions:
             return 4 * self.model.store.n
+        tail = 4 * (self.tail[1] - self.tail[0]) if self.tail is not None else 0
         for k in reversed(range(self.S)):
             if self.reduced[k]:
                 lo, hi = self.regions[k]
-                return 4 * (hi - lo)
+                return 4 * (hi - lo) + tail
             if self.active[k]:
-                return 0
-        return 0
+                return tail
+        return tail
 
     def _reduce_async(self, k):
         lo, hi = self.regions[k]
@@ -366,6 +381,10 @@ class DDPStep:
                     self._g_stage[k].replay() if self.use_graph else self._stage(k)
                 if self.reduced[k]:
                     works.append(self._reduce_async(k))
+            if self.tail is not None:
+                works.append(dist.all_reduce(self.model.store.flat_grad[self.tail[0]:self.tail[1]],
+                                             op=dist.ReduceOp.SUM, async_op=True,
+                                             group=self.reducer.group))
             self._t5_ext_join()
             for w in works:
                 w.wait()

@@ -96,8 +96,21 @@ class OctoConfig:
     # (upstream Octo's n_diffusion_samples; YAML key action_heads.n_diffusion_samples), 1 .. 64.
     # Above 1 the loss runs the fused multi-draw kernel (DiffusionActionHead.loss_forward_multi)
     n_diffusion_samples: int = 1
+    # the value tokenizer behind the Value{n} sets of input_sequence (proprioception;
+    # tokenizers/numeric_values/value_tokenizer.py; YAML key tokenizers.values.encoder): a dict
+    # with any of num_bins (2 .. 4096, default 256), mu (> 0, default 255.0, the reference's) and
+    # encoding ("mu_law", the default, or "uniform"). None with Value sets present: the defaults
+    value_tokenizer: Optional[dict] = None
 
     def __post_init__(self):
+        if self.value_tokenizer is not None:
+            from ...tokenizers.numeric_values.value_tokenizer import check_value_config
+            vt = self.value_tokenizer
+            if not isinstance(vt, dict) or set(vt) - {"num_bins", "mu", "encoding"}:
+                raise ValueError("value_tokenizer must be a dict with keys among num_bins, mu, "
+                                 f"encoding, got {vt!r}")
+            check_value_config(vt.get("num_bins", 256), vt.get("mu", 255.0),
+                               vt.get("encoding", "mu_law"))
         n = self.n_diffusion_samples
         if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 64:
             raise ValueError(f"n_diffusion_samples must be an integer in 1 .. 64, got {n!r}")
@@ -179,6 +192,12 @@ PRESETS = {
     # top-k pruning on the small geometry: 16 image tokens per block
     "octo-small-prune16": OctoConfig(name="octo-small-prune16", token_compression_sequence=TOME16,
                                      compression="prune"),
+    # configs[2] with 8 proprioception values per observation (Value tokens, never compressed)
+    "octo-small-tome16-proprio8": OctoConfig(
+        name="octo-small-tome16-proprio8",
+        input_sequence="[TaskDescriptionPrefix{32}] [Image{256};Value{8};Readout{4}]",
+        token_compression_sequence="[TaskDescriptionPrefix{0}] [Image{16};Value{0};Readout{0}]",
+        value_tokenizer=dict(num_bins=256, mu=255.0, encoding="mu_law")),
 }
 
 

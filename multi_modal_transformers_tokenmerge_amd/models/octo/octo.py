@@ -5,7 +5,8 @@ create_octo_train_state :334-386).
 
 MI355X design of the step (SURVEY §3.1 call stack):
   tokenizers  : frozen T5 (bf16 GEMM/attention kernels) -> Dense(768->D) [build addition for D!=768];
-                image stem kernels; device-drawn patch positions
+                image stem kernels; device-drawn patch positions; value tokens (proprioception:
+                mu-law bins -> a shared embedding table, tokenizers/numeric_values)
   sequence    : ONE fused kernel writes the token sequence (text | image + row/col emb | readout
                 embedding) + the learned position embedding; the blockwise mask is a token-set
                 table evaluated inside the attention kernel, never an (B, H, L, L) tensor
@@ -47,10 +48,11 @@ from ...tokenizers.images.image_tokenizer import ImageTokenizer
 from ...tokenizers.readout.readout import AddPositionEmbedding
 from ...tokenizers.text.t5_base import T5Tokenizer
 from ...tokenizers.token_compression import MergeSource
-from ...tokenizers.token_sequencer import Image, Readout, Text, TokenSequence
+from ...tokenizers.numeric_values.value_tokenizer import ValueTokenizer
+from ...tokenizers.token_sequencer import Image, Readout, Text, TokenSequence, Value
 from .config import OctoConfig, get_config
 
-KIND_TEXT, KIND_IMAGE, KIND_READOUT = 0, 1, 2
+KIND_TEXT, KIND_IMAGE, KIND_READOUT, KIND_VALUE = 0, 1, 2, 3
 
 
 class Octo:
@@ -73,6 +75,12 @@ class Octo:
         self.n_images = sum(isinstance(ts, Image) for ts in sets0)
         self.n_text = sum(ts.num_tokens for ts in sets0 if isinstance(ts, Text))
         self.n_readout = sum(ts.num_tokens for ts in sets0 if isinstance(ts, Readout))
+        self.n_value_sets = sum(isinstance(ts, Value) for ts in sets0)
+        self.n_values = sum(ts.num_tokens for ts in sets0 if isinstance(ts, Value))
+        for ts in sets0:
+            if isinstance(ts, Value) and ts.tokens_compressed_per_layer:
+                raise ValueError("Value sets are never compressed: token_compression_sequence must "
+                                 f"give them {{0}}, got {{{ts.tokens_compressed_per_layer}}}")
         self.has_text = self.n_text > 0
         if self.has_text and cfg.text_tokens != self.n_text:
             raise ValueError("text_tokens must equal the text set sizes of input_sequence")
@@ -125,6 +133,14 @@ class Octo:
                 cfg.pooling_heads or cfg.num_heads, cfg.pooling_mlp_dim or D, cfg.layer_norm_eps,
                 cfg.pooling_norm_axes)
             self.head.attach_pooling(self.pooling)
+        # value tokens: declared last of all and only with Value sets in the sequence, so every
+        # configuration without them keeps its parameter offsets and seeded initial values
+        self.value_tokenizer = None
+        if self.n_values:
+            self.value_tokenizer = ValueTokenizer(**(cfg.value_tokenizer or {})).bind(
+                store, "ValueTokenizer_0", D)
+        elif cfg.value_tokenizer is not None:
+            raise ValueError("value_tokenizer is set but input_sequence has no Value set")
         store.materialize(self.device, seed)
         # MMT_DETERMINISTIC=1: bitwise-reproducible gradients (ParamStore.set_deterministic)
         if os.environ.get("MMT_DETERMINISTIC", "0") == "1" and torch.device(self.device).type == "cuda":
@@ -139,22 +155,30 @@ class Octo:
         cfg = self.cfg
         NP = self.image_tokenizer.num_patches
         row_src = []
-        ti = ii = ri = 0
+        ti = ii = ri = vi = 0
         for ts in self.seq.token_sequence:
             for j in range(ts.num_tokens):
                 if isinstance(ts, Text):
                     row_src.append((KIND_TEXT << 24) | (ti + j))
                 elif isinstance(ts, Image):
                     row_src.append((KIND_IMAGE << 24) | (ii * NP + j))
+                elif isinstance(ts, Value):   # rows the sequence assembly leaves to the tokenizer
+                    row_src.append((KIND_VALUE << 24) | (vi + j))
                 else:
                     row_src.append((KIND_READOUT << 24) | (ri + j))
             if isinstance(ts, Text):
                 ti += ts.num_tokens
             elif isinstance(ts, Image):
                 ii += 1
+            elif isinstance(ts, Value):
+                vi += ts.num_tokens
             else:
                 ri += ts.num_tokens
         self.row_src = torch.tensor(row_src, dtype=torch.int32, device=self.device)
+        # value (set-major, slot) -> sequence row
+        self.value_rows = torch.tensor([row for row, v in enumerate(row_src)
+                                        if v >> 24 == KIND_VALUE], dtype=torch.int32,
+                                       device=self.device)
         img_rows = np.zeros(ii * NP, np.int32)                 # image token -> sequence row
         for row, v in enumerate(row_src):
             if v >> 24 == KIND_IMAGE:
@@ -226,13 +250,41 @@ class Octo:
         return ctxs
 
     # ------------------------------------------------------------------ forward / backward
+    def _check_values(self, values, B: int):
+        """The `values` argument as the (B, n_values) fp32 matrix the tokenizer reads, None for a
+        model without Value sets. ValueError: values missing from a model with Value sets, given
+        to one without, not an fp32 tensor on the model's device, or of a shape other than
+        (B, n_sets, n) / (B, n_sets * n)."""
+        if not self.n_values:
+            if values is not None:
+                raise ValueError("values given, but input_sequence has no Value set")
+            return None
+        if values is None:
+            raise ValueError(f"input_sequence has Value sets: pass values, fp32 "
+                             f"(B, {self.n_value_sets}, n) or (B, {self.n_values})")
+        if not torch.is_tensor(values) or values.dtype != torch.float32:
+            raise ValueError("values must be an fp32 tensor")
+        if values.device.type != self.device.type:
+            raise ValueError(f"values must live on the model's device ({self.device.type})")
+        flat = values.dim() == 2 and tuple(values.shape) == (B, self.n_values)
+        sets = values.dim() == 3 and values.shape[:2] == (B, self.n_value_sets) and \
+            values.shape[1] * values.shape[2] == self.n_values
+        if not (flat or sets):
+            raise ValueError(f"values {tuple(values.shape)}: expected ({B}, {self.n_value_sets}, "
+                             f"n) or ({B}, {self.n_values})")
+        return values.reshape(B, self.n_values)
+
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
-                          positions=None, tome=None, t5_out=None):
+                          positions=None, tome=None, t5_out=None, values=None):
         """Reference :91-126. Returns the final sequence (B, L_final, D) and the saved state.
         t5_out: the frozen T5 encoder's output for text_tokens, computed ahead (DDPStep's
-        cross-step T5 pipeline); None runs the encoder here."""
+        cross-step T5 pipeline); None runs the encoder here. values: the numbers behind the
+        Value sets, fp32 (B, n_sets, n) or (B, n_sets * n), expected in [-1, 1]
+        (tokenizers/numeric_values/value_tokenizer.py); required with Value sets in
+        input_sequence, refused without."""
         B = images.shape[0]
         D = self.D
+        values = self._check_values(values, B)
         st: Dict = dict(B=B, train=train, rng=rng, sample_offset=sample_offset)
         txt, T = None, max(self.n_text, 1)
         if self.has_text:
@@ -254,6 +306,9 @@ class Octo:
                 _C.ptr(img_tok), NI, _C.ptr(rt), _C.ptr(ct), _C.ptr(self.image_tokenizer.row_emb.data),
                 _C.ptr(self.image_tokenizer.col_emb.data), _C.ptr(self.readout_pe.data),
                 _C.ptr(self.pos_embed.data), _C.ptr(x0), _C.stream_ptr())
+        if values is not None:  # the rows of kind 3, which the assembly skipped
+            st["val_tok"] = self.value_tokenizer.forward(values, self.value_rows,
+                                                         self.pos_embed.data, x0)
         ctxs = self.layer_ctxs(train, rng, sample_offset)
         if tome is not None:  # injected ToMe index triples (tests: the golden step fixtures)
             for c, idx in zip(ctxs, tome):
@@ -288,7 +343,7 @@ class Octo:
 
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
                                        sample_offset=0, inject: Optional[dict] = None, t5_out=None,
-                                       action_pad_mask=None):
+                                       action_pad_mask=None, values=None):
         """Reference :139-145. Returns (loss (1,) fp32 device tensor, saved state). inject (tests):
         positions (rt, ct), t, eps, tome (per block an (unm, src, dst) triple of int32 device
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
@@ -298,7 +353,7 @@ class Octo:
         which is normalised by the number of real components. With it, or with
         OctoConfig.n_diffusion_samples = K > 1 (K independent (t, eps) draws per sample; inject
         t (K, B) / eps (K, B, h a)), the head runs its fused multi-draw loss on the pooled readout
-        (DiffusionActionHead.loss_forward_multi)."""
+        (DiffusionActionHead.loss_forward_multi). values: generate_readouts'."""
         inject = inject or {}
         actions = self._chunk_flat(actions)
         multi = self.cfg.n_diffusion_samples > 1 or action_pad_mask is not None
@@ -309,7 +364,8 @@ class Octo:
             if action_pad_mask.shape[0] != actions.shape[0]:
                 raise ValueError("action_pad_mask and actions differ in batch size")
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                        inject.get("positions"), inject.get("tome"), t5_out)
+                                        inject.get("positions"), inject.get("tome"), t5_out,
+                                        values=values)
         B = xL.shape[0]
         if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
             cat = None
@@ -344,22 +400,24 @@ class Octo:
         return chunk_flat(actions, h, self.cfg.action_space_dim)
 
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
-                                       sample_offset=0, train=True):
+                                       sample_offset=0, train=True, values=None):
         """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
         pooling) -> OctoDenoise (diffusion.py:88-107)."""
-        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
+        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
+                                       values=values)
         return self.head.predict_denoise_term_mean(self._readout_pooled(xL), time, noisy_actions)
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
-                                 positions=None, sampler=None):
+                                 positions=None, sampler=None, values=None):
         """Reference :147-154: readouts (the reference's backbone always runs with
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
         the sampler (action_heads/diffusion.py:146-209): `sampler` (a SamplerSpec or a dict of its
         fields), else OctoConfig.sampler, else the reference's 32-step DDPM loop. Returns fp32
         (B, action_space_dim), or (B, action_horizon, action_space_dim) with a horizon > 1 (z
         and the returned noise stay flat, (B, h a))."""
-        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions)
+        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions,
+                                       values=values)
         if self.pooling is not None:
             e = self._readout_pooled(xL)
         else:
@@ -408,10 +466,12 @@ class Octo:
             raise ValueError(f"{name} head not built: add it to OctoConfig.action_heads")
         return head
 
-    def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True):
+    def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
+                                  values=None):
         """Reference :158-165 -> (B, pred_horizon, A) fp32 ((B, 1, A) as the reference)."""
         h = self._need(self.continuous_head, "continuous")
-        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
+        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
+                                       values=values)
         return h.forward(self._readout_mean(xL))
 
     @staticmethod
@@ -420,7 +480,7 @@ class Octo:
             raise ValueError("action_pad_mask must be a bool tensor")
 
     def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None):
+                        action_pad_mask=None, values=None):
         """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved).
         actions (B, pred_horizon, A) or flat; OctoConfig.continuous_loss picks the squared error
         or L1. action_pad_mask: bool, the actions' shape, True where a component is real: padded
@@ -428,36 +488,41 @@ class Octo:
         of real components (as compute_diffusion_denoise_loss)."""
         h = self._need(self.continuous_head, "continuous")
         self._check_pad_mask(action_pad_mask)
-        xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
+        xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
+                                        values=values)
         loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
-    def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True):
+    def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True,
+                              values=None):
         """Reference :178-185 -> (B, A, num_bins) fp32, (B, pred_horizon, A, num_bins) with a
         pred_horizon > 1."""
         h = self._need(self.categorical_head, "categorical")
-        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
+        xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
+                                       values=values)
         return h.forward(self._readout_group_means(xL))
 
     def predict_categorical_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                                   mode="argmax", temperature=1.0):
+                                   mode="argmax", temperature=1.0, values=None):
         """The categorical head rolled out: logits (predict_action_logits) decoded to actions
         (B, pred_horizon, A) fp32 through bin_values, by argmax or (mode "sample") one draw per
         component from softmax(logits / temperature) keyed by rng and sample_offset
         (CategoricalActionHead.decode)."""
         h = self._need(self.categorical_head, "categorical")
-        logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train)
+        logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train,
+                                            values=values)
         return h.decode(logits, rng, sample_offset, mode, temperature)[0]
 
     def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None):
+                        action_pad_mask=None, values=None):
         """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved).
         actions (B, pred_horizon, A) or flat. action_pad_mask: compute_l2_loss's; the loss is the
         mean of the cross entropy over the real components."""
         h = self._need(self.categorical_head, "categorical")
         self._check_pad_mask(action_pad_mask)
-        xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset)
+        xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
+                                        values=values)
         loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
@@ -506,15 +571,18 @@ class Octo:
         backward has to reach: the lowest block holding a trainable parameter (nb if none does),
         or 0 while a parameter before the blocks is trained, whose gradient comes through all of
         them. The backward runs blocks [j, nb) and the token / stem part only for j == 0 and not
-        tokens_frozen; with j == nb the heads do not produce the sequence gradient at all."""
+        tokens_frozen; with j == nb the heads do not produce the sequence gradient at all. The
+        value tokenizer's embedding is a token-level parameter like those before block 0, though
+        it is declared after the heads (Octo.__init__)."""
         nb = self.cfg.num_blocks
         off0 = self._block_offset(0)
         pre = "StackedEncoder1DBlock_0/Block_"
+        vpre = "ValueTokenizer_0/"
         tokens_frozen, j = True, nb
         for p in self.store.params:
             if p.frozen:
                 continue
-            if p.offset < off0:
+            if p.offset < off0 or p.name.startswith(vpre):
                 tokens_frozen = False
             elif p.name.startswith(pre):
                 j = min(j, int(p.name[len(pre):].split("/", 1)[0]))
@@ -575,16 +643,27 @@ class Octo:
     def grad_regions(self, stages) -> List[tuple]:
         """Flat-gradient index ranges that are final after each backward stage (stage 0: the
         heads and the last blocks, declared last in the store; the last stage: the first blocks
-        and everything declared before them). `stages` as in stage_bounds."""
+        and everything declared before them). `stages` as in stage_bounds. With Value sets and
+        more than one stage, stage 0's region ends where tail_region() starts."""
         b = self.stage_bounds(stages)
         n_stages = len(b) - 1
         off = [self._block_offset(j) for j in b]
+        tail = self.tail_region()
+        top = tail[0] if tail is not None and n_stages > 1 else self.store.n
         regions = []
         for i in range(n_stages):
-            hi = self.store.n if i == 0 else off[i]
+            hi = top if i == 0 else off[i]
             lo = 0 if i == n_stages - 1 else off[i + 1]
             regions.append((lo, hi))
         return regions
+
+    def tail_region(self) -> Optional[tuple]:
+        """The flat-gradient range of the value tokenizer's embedding, None without Value sets:
+        declared after the heads, but written by the token backward, so it is final only after
+        the LAST stage (DDPStep all-reduces it there, beside that stage's own region)."""
+        if self.value_tokenizer is None:
+            return None
+        return self.value_tokenizer.embedding.offset, self.store.n
 
     def backward_stage(self, st: Dict, stage: int, stages):
         """Stage `stage` of a backward split as stage_bounds(stages) (the heads run in stage 0,
@@ -682,6 +761,8 @@ class Octo:
                     _C.ptr(st["rt"]), _C.ptr(st["ct"]), _C.ptr(it.row_emb.grad),
                     _C.ptr(it.col_emb.grad), _C.stream_ptr())
         K.colsum(dx0.view(B, self.L0 * D), self.pos_embed.grad.view(-1))
+        if self.value_tokenizer is not None:
+            self.value_tokenizer.backward(dx0, st["val_tok"], self.value_rows)
         it.backward(dimg, st["img_sv"])
         if self.text_proj is not None:
             self.text_proj.bwd(dtxt.view(B * T, D), st["t5_out"].view(B * T, -1), need_dx=False)
@@ -1024,30 +1105,38 @@ def _train_step(loss_fn, model: Octo, train_state: OCTOTrainState, text_tokens, 
     return train_state, grads_tree(model)
 
 
-def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                          action_pad_mask=None):
-    """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads). action_pad_mask: compute_l2_loss's."""
+def _step_kw(action_pad_mask, values) -> dict:
+    """The optional keywords of a loss, passed only when given."""
     kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
+    if values is not None:
+        kw["values"] = values
+    return kw
+
+
+def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
+                          action_pad_mask=None, values=None):
+    """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
+    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_l2_loss's."""
+    kw = _step_kw(action_pad_mask, values)
     return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                           action_pad_mask=None):
+                           action_pad_mask=None, values=None):
     """Reference octo.py:282-320: value_and_grad of mean(compute_ce_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads). action_pad_mask: compute_ce_loss's."""
-    kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
+    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_ce_loss's."""
+    kw = _step_kw(action_pad_mask, values)
     return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                         inject: Optional[dict] = None, action_pad_mask=None):
+                         inject: Optional[dict] = None, action_pad_mask=None, values=None):
     """Reference octo.py:204-240: value_and_grad of the denoise loss, apply_gradients, metrics
     merge. Returns (train_state, grads) like the reference; grads are views of the flat gradient
     buffer by parameter name, the loss is train_state.last_loss (device) and the running average
-    train_state.metrics. action_pad_mask: compute_diffusion_denoise_loss's."""
-    kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
+    train_state.metrics. action_pad_mask, values: compute_diffusion_denoise_loss's."""
+    kw = _step_kw(action_pad_mask, values)
     return _train_step(model.compute_diffusion_denoise_loss, model, train_state, text_tokens,
                        images, actions, inject=inject, **kw)

@@ -1,6 +1,8 @@
 """Token sequence grammar and blockwise attention rules, mirroring the reference's
 ``multi_modal_transformers/tokenizers/token_sequencer.py`` (TokenSet :20-52, Text :55-91,
-TaskDescriptionPrefix :94-113, Image :116-148, Readout :151-183, TokenSequence :186-340).
+TaskDescriptionPrefix :94-113, Image :116-148, Readout :151-183, TokenSequence :186-340), plus a
+fourth class the reference's grammar lacks: Value, the tokens of low-dimensional numbers
+(tokenizers/numeric_values/value_tokenizer.py), with Image's rules.
 
 The reference materialises the (H, L, L) boolean mask with Python loops on every apply
 (:313-321). Here that dense form exists for API parity and tests only; the hot path consumes the
@@ -100,6 +102,20 @@ class Image(TokenSet):
         return "ones"
 
 
+class Value(TokenSet):
+    """Value tokens (proprioception; tokenizers/numeric_values/value_tokenizer.py), Image's rules:
+    the Value sets of its own timestep + every non-readout set with t' <= t. Never compressed."""
+    modality = "values"
+
+    def inter_kind(self, other):
+        if isinstance(other, Readout):
+            return "zeros"
+        return "ones" if other.timestep <= self.timestep else "zeros"
+
+    def intra_kind(self):
+        return "ones"
+
+
 class Readout(TokenSet):
     """Reference :151-183: own set + every non-readout set with t' <= t."""
     modality = "readouts"
@@ -114,7 +130,7 @@ class Readout(TokenSet):
 
 
 _CLASSES = {"Text": Text, "TaskDescriptionPrefix": TaskDescriptionPrefix, "Image": Image,
-            "Readout": Readout}
+            "Value": Value, "Readout": Readout}
 
 
 @dataclass
@@ -123,6 +139,7 @@ class TokenEmbeddings:
     text: object = None
     images: object = None
     readouts: object = None
+    values: object = None
 
 
 @dataclass
@@ -187,7 +204,7 @@ class TokenSequence:
 
     # ------------------------------------------------------------------ slices (:272-304)
     def _generate_embedding_slices(self):
-        idx = {"images": 0, "text": 0, "readouts": 0}
+        idx = {"images": 0, "text": 0, "readouts": 0, "values": 0}
         out = []
         for ts in self.token_sequence:
             out.append((idx[ts.modality], ts.num_tokens))
