@@ -48,7 +48,8 @@ int mmt_version(void);
 /* Device-side index checks. The entry points that address memory through caller-supplied index
  * arrays (mmt_tome_merge_wavg_fwd / _bwd, mmt_tome_merge_seqnorm_fwd, mmt_ln_unmerge_dropout_bwd,
  * mmt_gather_rows, mmt_topk_scatter_bwd, mmt_tome_pos_map, mmt_tome_source_step / _groups,
- * mmt_tome_unmerge_fwd / _bwd, mmt_value_tokens_fwd / _bwd) cannot see those device values at
+ * mmt_tome_unmerge_fwd / _bwd, mmt_value_tokens_fwd / _bwd, mmt_pc_sample_group,
+ * mmt_pc_embed_fwd / _bwd) cannot see those device values at
  * launch. Their kernels
  * range-check every index they use; an invalid one is replaced by 0 (so no access leaves its
  * tensor and the context survives) and sets a bit of a library-wide device status word:
@@ -663,7 +664,8 @@ int mmt_patch_positions(const uint32_t* rng, uint32_t site, int B, int I, int Hi
 /* ------------------------------------------------------------------ sequence assembly
  * x0[b, l] = source(l) + pe[l] with source = text[b, j] | img[b, j] + row_emb[rtok] + col_emb[ctok]
  * | readout_pe[j]  (row_src[l] = kind << 24 | j, kind 0 text / 1 image / 2 readout; a row of
- * kind 3, a value token, is left untouched by both directions: mmt_value_tokens_fwd / _bwd):
+ * kind 3, a value token, or 4, a point-cloud token, is left untouched by both directions:
+ * mmt_value_tokens_fwd / _bwd, mmt_pc_embed_fwd / _bwd):
  * TokenSequence.assemble_embeddings (token_sequencer.py:255-269), readout AddPositionEmbedding
  * on zeros (readout.py:18-33, octo.py:103-108), ImageTokenizer embeddings (:300-307) and the
  * encoder's learned position embedding (attention.py:71-85,97-100), fused. fp32 tables.
@@ -748,6 +750,69 @@ int mmt_value_tokens_fwd(const float* values, int64_t ld_v, int B, int n, int en
 int mmt_value_tokens_bwd(const void* dx0, int64_t xs_b, int64_t xs_t, int B, int n,
                          const int32_t* tok, const int32_t* rows, int D, int num_bins,
                          float* dtable, mmt_stream_t stream);
+
+/* ------------------------------------------------------------------ point-cloud tokens
+ * A point cloud (P, C) fp32 (the first three features are xyz; C in 3 .. 8, the extras colour or
+ * normals) as n sequence rows, one per sampled centroid with its neighbourhood (csrc/
+ * pointcloud.hip): the reference's tokenizers/pointclouds/point_cloud_tokenizer.py (farthest-point
+ * sampling :42-92, kNN grouping :106-116, SampleAndGroupModule :119-198), restated. All fp32.
+ *   d(p, c) = (dx dx + dy dy) + dz dz, dx = p.x - c.x ..., every operation individually rounded
+ *             (no FMA): numpy float32 reproduces it bit for bit
+ *   sampling: dist = +inf, ids[0] = start; for i = 1 .. n-1: dist = min(dist, d(., ids[i-1])),
+ *             ids[i] = argmax over the points not yet sampled, the lowest index on ties
+ *   grouping: per centroid the k points of smallest d, ascending by (d, index)
+ *   features: neighbour j of centroid c: [points[j] - points[c], points[j]] (2 C numbers)
+ *   embedding: h1 = relu(feat W1 + b1), h2 = relu(h1 W2 + b2), g = max over the k neighbours of
+ *             h2, row = (g W_out + b_out) + pe[row]; W1 (2C, F1), W2 (F1, F2), W_out (F2, D),
+ *             F1, F2 in {32, 64, 128}
+ * Limits (MMT_ERR_INVALID before a launch): max(n, k) <= P <= MMT_PC_MAX_POINTS, 1 <= n <=
+ * MMT_PC_MAX_TOKENS, 1 <= k <= MMT_PC_MAX_NEIGHBOURS, MMT_PC_MIN_FEATURES <= C <=
+ * MMT_PC_MAX_FEATURES. points: cloud (b, s) starts at points + b ld_b + s ld_s (elements) and is
+ * contiguous (P, C). Non-finite coordinates are the caller's error: every index written is still
+ * in [0, P), the result is otherwise unspecified.
+ *
+ * mmt_pc_sample_group: centroid_idx (B, S, n) and neighbour_idx (B, S, n, k) int32. The start of
+ * cloud (b, s) is start[b S + s] if start is non-null (outside [0, P): 0 and
+ * MMT_FAULT_ROW_INDEX), else, with rng (the two-word RNG state) non-null, the draw
+ * (draw_u32(stream_key(seed, step, 0xFFF7, 1), (sample_offset + b) S + s) * P) >> 32, else 0. */
+#define MMT_PC_MAX_POINTS 4096
+#define MMT_PC_MAX_TOKENS 256
+#define MMT_PC_MAX_NEIGHBOURS 32
+#define MMT_PC_MIN_FEATURES 3
+#define MMT_PC_MAX_FEATURES 8
+#define MMT_PC_MAX_WIDTH 4096
+int mmt_pc_sample_group(const float* points, int64_t ld_b, int64_t ld_s, int B, int S, int P, int C,
+                        int n, int k, const int32_t* start, const uint32_t* rng,
+                        int64_t sample_offset, int32_t* centroid_idx, int32_t* neighbour_idx,
+                        mmt_stream_t stream);
+/* Forward of the embedding: writes x0[b, rows[s n + m], :] for token m of cloud (b, s) and no
+ * other row (mmt_seq_assemble_fwd skips the rows of kind 4, which these are), and argmax
+ * (B, S, n, F2) uint8, the first neighbour slot that attains each maximum. rows (S n,) int32; pe
+ * (L, D) fp32 contiguous; x0 fp32 with element strides xs_b, xs_t; D a multiple of 4, at most
+ * MMT_PC_MAX_WIDTH. An index of centroid_idx / neighbour_idx outside [0, P) is read as 0, a row
+ * outside its sample is not written: MMT_FAULT_ROW_INDEX. */
+int mmt_pc_embed_fwd(const float* points, int64_t ld_b, int64_t ld_s, int B, int S, int P, int C,
+                     int n, int k, const int32_t* centroid_idx, const int32_t* neighbour_idx, int F1,
+                     int F2, const float* w1, const float* b1, const float* w2, const float* b2,
+                     const float* w_out, const float* b_out, const float* pe, const int32_t* rows,
+                     int D, void* x0, int64_t xs_b, int64_t xs_t, uint8_t* argmax,
+                     mmt_stream_t stream);
+/* Backward: the gradients of the six parameter tensors from the rows of dx0 (none reaches the
+ * points; d(pe) is mmt_colsum over dx0). The hidden activations are recomputed. The max routes
+ * its gradient to the saved arg-max slot; relu'(0) = 0. Token chunks of a size that depends on
+ * B S n alone write partial gradients with one owner per element to the workspace; each gradient
+ * element is then the sum of its partials in ascending chunk order, added ONCE to the gradient
+ * buffer: no float atomics, bitwise reproducible with and without the deterministic mode.
+ * workspace: >= mmt_pc_embed_bwd_workspace(...) bytes, 16-B aligned. An argmax entry >= k is read
+ * as 0: MMT_FAULT_ROW_INDEX. */
+int64_t mmt_pc_embed_bwd_workspace(int B, int S, int n, int C, int F1, int F2, int D);
+int mmt_pc_embed_bwd(const void* dx0, int64_t xs_b, int64_t xs_t, const int32_t* rows, int D,
+                     const float* points, int64_t ld_b, int64_t ld_s, int B, int S, int P, int C,
+                     int n, int k, const int32_t* centroid_idx, const int32_t* neighbour_idx,
+                     const uint8_t* argmax, int F1, int F2, const float* w1, const float* b1,
+                     const float* w2, const float* b2, const float* w_out, float* dw1, float* db1,
+                     float* dw2, float* db2, float* dw_out, float* db_out, void* workspace,
+                     int64_t workspace_bytes, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ attention pooling
  * MultiHeadAttentionPooling (attention_blocks/attention.py:122-150) of the readout tokens, the

@@ -1165,3 +1165,121 @@ def value_tokens_bwd(dx0: torch.Tensor, tok: torch.Tensor, rows: torch.Tensor,
     _C.call("mmt_value_tokens_bwd", ptr(dx0), dx0.stride(0), dx0.stride(1), B, n, ptr(tok),
             ptr(rows), D, dtable.shape[0], ptr(dtable), _C.stream_ptr())
     return dtable
+
+
+# ------------------------------------------------------------------------------- point-cloud tokens
+def check_pc_limits(P: int, C: int, n: int, k: int, F1: int | None = None, F2: int | None = None):
+    """ValueError unless max(n, k) <= P <= 4096, 1 <= n <= 256, 1 <= k <= 32, 3 <= C <= 8 and
+    (when given) F1, F2 in {32, 64, 128}: the limits of mmt_pc_sample_group / mmt_pc_embed_*."""
+    for v, what in ((P, "num_points"), (C, "point_features"), (n, "the token count"),
+                    (k, "num_neighbours_knn")):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what} must be an integer, got {v!r}")
+    if not _C.PC_MIN_FEATURES <= C <= _C.PC_MAX_FEATURES:
+        raise ValueError(f"point_features must be in {_C.PC_MIN_FEATURES} .. "
+                         f"{_C.PC_MAX_FEATURES}, got {C}")
+    if not 1 <= n <= _C.PC_MAX_TOKENS:
+        raise ValueError(f"a cloud gives 1 .. {_C.PC_MAX_TOKENS} tokens, got {n}")
+    if not 1 <= k <= _C.PC_MAX_NEIGHBOURS:
+        raise ValueError(f"num_neighbours_knn must be in 1 .. {_C.PC_MAX_NEIGHBOURS}, got {k}")
+    if not max(n, k) <= P <= _C.PC_MAX_POINTS:
+        raise ValueError(f"num_points must be in max(n, k) = {max(n, k)} .. {_C.PC_MAX_POINTS}, "
+                         f"got {P}")
+    for F in (F1, F2):
+        if F is not None and (isinstance(F, bool) or F not in _C.PC_HIDDEN_WIDTHS):
+            raise ValueError(f"hidden widths must be among {_C.PC_HIDDEN_WIDTHS}, got {F!r}")
+
+
+def _pc_points(points: torch.Tensor):
+    """(B, S, P, C) fp32 whose clouds are contiguous -> (B, S, P, C, ld_b, ld_s)."""
+    if points.dim() != 4 or points.dtype != torch.float32:
+        raise ValueError("points must be fp32 (B, S, P, C)")
+    B, S, P, C = points.shape
+    if points.stride(3) != 1 or points.stride(2) != C or (S > 1 and points.stride(1) < P * C) or \
+            (B > 1 and points.stride(0) < (S - 1) * points.stride(1) + P * C):
+        raise ValueError("points: every (P, C) cloud must be contiguous (the batch and set "
+                         "strides may be padded)")
+    ld_s = points.stride(1) if S > 1 else P * C
+    ld_b = points.stride(0) if B > 1 else S * ld_s
+    return B, S, P, C, ld_b, ld_s
+
+
+def pc_sample_group(points: torch.Tensor, n: int, k: int, start: torch.Tensor | None = None,
+                    rng: torch.Tensor | None = None, sample_offset: int = 0):
+    """Farthest-point sampling and kNN grouping of every cloud of points (B, S, P, C) fp32
+    (mmt_pc_sample_group): (centroid_idx (B, S, n), neighbour_idx (B, S, n, k)) int32. The first
+    centroid: start (B, S) int32 if given, else drawn from rng (the two-word RNG state) for the
+    global cloud index (sample_offset + b) * S + s, else point 0."""
+    _dev(points, start, rng)
+    B, S, P, C, ld_b, ld_s = _pc_points(points)
+    check_pc_limits(P, C, n, k)
+    if start is not None:
+        _check_i32(start, (B, S), "start")
+    cidx = torch.empty((B, S, n), dtype=torch.int32, device=points.device)
+    nidx = torch.empty((B, S, n, k), dtype=torch.int32, device=points.device)
+    _C.call("mmt_pc_sample_group", ptr(points), ld_b, ld_s, B, S, P, C, n, k, ptr(start), ptr(rng),
+            int(sample_offset), ptr(cidx), ptr(nidx), _C.stream_ptr())
+    return cidx, nidx
+
+
+def _pc_weights(C: int, w1, b1, w2, b2, w_out, b_out):
+    F1, F2, D = w1.shape[1], w2.shape[1], w_out.shape[1]
+    for t, shape, what in ((w1, (2 * C, F1), "w1"), (b1, (F1,), "b1"), (w2, (F1, F2), "w2"),
+                           (b2, (F2,), "b2"), (w_out, (F2, D), "w_out"), (b_out, (D,), "b_out")):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous fp32 {shape}, got {tuple(t.shape)}")
+    return F1, F2, D
+
+
+def _pc_rows(x: torch.Tensor, rows: torch.Tensor, B: int, S: int, n: int, D: int, what: str):
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1 or x.shape[0] != B or \
+            x.shape[2] != D:
+        raise ValueError(f"{what} must be fp32 ({B}, L, {D}) with unit inner stride")
+    _check_i32(rows, (S * n,), "rows")
+
+
+def pc_embed_fwd(points, cidx, nidx, w1, b1, w2, b2, w_out, b_out, pe, rows, x0):
+    """The rows of the point-cloud tokens (mmt_pc_embed_fwd): x0[b, rows[s n + m]] =
+    (max_k relu(relu(feat W1 + b1) W2 + b2)) W_out + b_out + pe[rows[s n + m]] and no other row of
+    x0 (B, L, D) fp32 (strided). Returns argmax (B, S, n, F2) uint8, the backward's saved state."""
+    _dev(points, cidx, nidx, w1, b1, w2, b2, w_out, b_out, pe, rows, x0)
+    B, S, P, C, ld_b, ld_s = _pc_points(points)
+    n, k = cidx.shape[-1], nidx.shape[-1]
+    F1, F2, D = _pc_weights(C, w1, b1, w2, b2, w_out, b_out)
+    check_pc_limits(P, C, n, k, F1, F2)
+    _check_i32(cidx, (B, S, n), "centroid_idx")
+    _check_i32(nidx, (B, S, n, k), "neighbour_idx")
+    _pc_rows(x0, rows, B, S, n, D, "x0")
+    if pe.dtype != torch.float32 or tuple(pe.shape) != (x0.shape[1], D) or not pe.is_contiguous():
+        raise ValueError(f"pe must be contiguous fp32 {(x0.shape[1], D)}")
+    argmax = torch.empty((B, S, n, F2), dtype=torch.uint8, device=points.device)
+    _C.call("mmt_pc_embed_fwd", ptr(points), ld_b, ld_s, B, S, P, C, n, k, ptr(cidx), ptr(nidx), F1,
+            F2, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w_out), ptr(b_out), ptr(pe), ptr(rows), D,
+            ptr(x0), x0.stride(0), x0.stride(1), ptr(argmax), _C.stream_ptr())
+    return argmax
+
+
+def pc_embed_bwd(dx0, rows, points, cidx, nidx, argmax, w1, b1, w2, b2, w_out, grads):
+    """grads = (dw1, db1, dw2, db2, dw_out, db_out), fp32 like the weights: each += its gradient
+    from the rows dx0[b, rows[s n + m]] (mmt_pc_embed_bwd: chunk partials summed in a fixed order
+    and added once, no atomics)."""
+    dw1, db1, dw2, db2, dw_out, db_out = grads
+    _dev(dx0, rows, points, cidx, nidx, argmax, w1, b1, w2, b2, w_out, *grads)
+    B, S, P, C, ld_b, ld_s = _pc_points(points)
+    n, k = cidx.shape[-1], nidx.shape[-1]
+    F1, F2, D = _pc_weights(C, w1, b1, w2, b2, w_out, db_out)
+    _pc_weights(C, dw1, db1, dw2, db2, dw_out, db_out)
+    check_pc_limits(P, C, n, k, F1, F2)
+    _check_i32(cidx, (B, S, n), "centroid_idx")
+    _check_i32(nidx, (B, S, n, k), "neighbour_idx")
+    if argmax.dtype != torch.uint8 or tuple(argmax.shape) != (B, S, n, F2) or \
+            not argmax.is_contiguous():
+        raise ValueError(f"argmax must be contiguous uint8 {(B, S, n, F2)}")
+    _pc_rows(dx0, rows, B, S, n, D, "dx0")
+    nbytes = _C.call("mmt_pc_embed_bwd_workspace", B, S, n, C, F1, F2, D)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+    _C.call("mmt_pc_embed_bwd", ptr(dx0), dx0.stride(0), dx0.stride(1), ptr(rows), D, ptr(points),
+            ld_b, ld_s, B, S, P, C, n, k, ptr(cidx), ptr(nidx), ptr(argmax), F1, F2, ptr(w1),
+            ptr(b1), ptr(w2), ptr(b2), ptr(w_out), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2),
+            ptr(dw_out), ptr(db_out), ptr(ws), nbytes, _C.stream_ptr())
+    return grads

@@ -197,6 +197,11 @@ def _rules(model) -> Dict[str, Rule]:
         ["attention_blocks/posembed_input/pos_embedding"], _lead1, _drop1)
     if getattr(model, "value_tokenizer", None) is not None:  # the nn.Embed of the Value sets
         rules["ValueTokenizer_0/embedding"] = (["ValueTokenizer_0/embedding"], _ident, _ident)
+    if getattr(model, "point_cloud_tokenizer", None) is not None:  # the PointCloud sets' tokenizer
+        for leaf in ("LBR_1/kernel", "LBR_1/bias", "LBR_2/kernel", "LBR_2/bias",
+                     "output_dense/kernel", "output_dense/bias"):
+            name = f"PointCloudTokenizer_0/{leaf}"   # stored in the Flax (in, out) layout already
+            rules[name] = ([name], _ident, _ident)
     if model.text_proj is not None:  # this build's projection of T5 features to D (no reference twin)
         rules["TextProjection_0/kernel"] = (["TextProjection_0/kernel"], _dense_T, _dense_T)
         rules["TextProjection_0/bias"] = (["TextProjection_0/bias"], _ident, _ident)

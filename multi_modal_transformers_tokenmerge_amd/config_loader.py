@@ -24,7 +24,9 @@ which are not available on the GPU box.
   ``action_heads.sampler`` (its default SamplerSpec as a mapping), ``action_heads.pred_horizon``
   (the chunk length of the continuous and categorical heads) and
   ``action_heads.continuous_loss`` ("mse" | "l1"), ``tokenizers.values.encoder`` (the
-  ValueTokenizer node behind the ``Value{n}`` sets of the sequence), ``fp8_matmul``,
+  ValueTokenizer node behind the ``Value{n}`` sets of the sequence),
+  ``tokenizers.pointclouds.encoder`` (the PointCloudTokenizer node behind the ``PointCloud{n}``
+  sets, with ``num_points``), ``fp8_matmul``,
   ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
@@ -162,6 +164,7 @@ TARGETS = {
     _REF + "tokenizers.images.image_tokenizer.ResNetV2Block": _BUILD + "tokenizers.images.image_tokenizer.ResNetV2Block",
     _REF + "tokenizers.text.t5_base.T5Tokenizer": _BUILD + "tokenizers.text.t5_base.T5Tokenizer",
     _REF + "tokenizers.numeric_values.value_tokenizer.ValueTokenizer": _BUILD + "tokenizers.numeric_values.value_tokenizer.ValueTokenizer",
+    _REF + "tokenizers.pointclouds.point_cloud_tokenizer.PointCloudTokenizer": _BUILD + "tokenizers.pointclouds.point_cloud_tokenizer.PointCloudTokenizer",
     _REF + "action_heads.diffusion.DiffusionActionHead": _BUILD + "action_heads.diffusion.DiffusionActionHead",
     _REF + "action_heads.continuous.ContinuousActionHead": _BUILD + "action_heads.continuous.ContinuousActionHead",
     _REF + "action_heads.categorical.CategoricalActionHead": _BUILD + "action_heads.categorical.CategoricalActionHead",
@@ -309,6 +312,12 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     vt = _first(cfg, "tokenizers.values.encoder", default=None)
     if vt is not None:
         kw["value_tokenizer"] = {k: vt[k] for k in ("num_bins", "mu", "encoding") if k in vt}
+    # the point-cloud tokenizer of the PointCloud{n} sets: the _target_ node's own fields
+    pc = _first(cfg, "tokenizers.pointclouds.encoder", default=None)
+    if pc is not None:
+        keys = ("num_points", "num_neighbours_knn", "point_features", "hidden")
+        kw["point_cloud_tokenizer"] = {k: (tuple(pc[k]) if k == "hidden" else pc[k])
+                                       for k in keys if k in pc}
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

@@ -28,9 +28,11 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// row descriptor: kind << 24 | index   (kind 0 text row, 1 image row, 2 readout row, 3 value row:
-// written and differentiated by values.hip's kernels, skipped here)
-constexpr int KIND_TEXT = 0, KIND_IMAGE = 1, KIND_READOUT = 2, KIND_VALUE = 3;
+// row descriptor: kind << 24 | index   (kind 0 text row, 1 image row, 2 readout row, 3 value row,
+// 4 point-cloud row: written and differentiated by values.hip's and pointcloud.hip's kernels,
+// skipped here by one kind >= KIND_VALUE compare)
+constexpr int KIND_TEXT = 0, KIND_IMAGE = 1, KIND_READOUT = 2, KIND_VALUE = 3, KIND_POINT = 4;
+static_assert(KIND_POINT == KIND_VALUE + 1, "the skipped kinds are the highest");
 
 __global__ void seq_assemble_fwd_kernel(int B, int L, int D, const int32_t* __restrict__ row_src,
                                         const bf16_t* __restrict__ text, int T,
@@ -50,7 +52,7 @@ __global__ void seq_assemble_fwd_kernel(int B, int L, int D, const int32_t* __re
   const int d0 = ch * 8;
   const int desc = row_src[l];
   const int kind = desc >> 24, j = desc & 0xffffff;
-  if (kind == KIND_VALUE) return;  // mmt_value_tokens_fwd owns the row
+  if (kind >= KIND_VALUE) return;  // mmt_value_tokens_fwd / mmt_pc_embed_fwd own the row
   float v[8];
   if (kind == KIND_TEXT) {
     unpack8(*reinterpret_cast<const uint4*>(text + ((int64_t)b * T + j) * D + d0), v);
@@ -86,7 +88,7 @@ __global__ void seq_assemble_bwd_kernel(int B, int L, int D, const int32_t* __re
   const int d0 = ch * 8;
   const int desc = row_src[l];
   const int kind = desc >> 24, j = desc & 0xffffff;
-  if (kind == KIND_VALUE) return;  // mmt_value_tokens_bwd reads the row
+  if (kind >= KIND_VALUE) return;  // mmt_value_tokens_bwd / mmt_pc_embed_bwd read the row
   float v[8];
   {
     const float* gp = dx0 + ((int64_t)b * L + l) * D + d0;

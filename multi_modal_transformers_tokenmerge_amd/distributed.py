@@ -100,15 +100,22 @@ class DDPStep:
     #
     # values: the numbers behind the model's Value sets (Octo.generate_readouts), a static device
     # buffer read by every replay like img and act; required with Value sets, refused without.
+    # point_clouds: the clouds behind its PointCloud sets, a static device buffer likewise.
 
     def __init__(self, model, state, txt, img, act, reducer: GradAllReducer | None = None,
-                 stages="auto", use_graph: bool = True, txt_next=None, values=None):
+                 stages="auto", use_graph: bool = True, txt_next=None, values=None,
+                 point_clouds=None):
         self.model, self.state = model, state
         self.txt, self.img, self.act = txt, img, act
         if values is not None or model.n_values:    # ValueError now, not inside a capture
             model._check_values(values, img.shape[0])
         self.values = values
         self._vkw = {} if values is None else {"values": values}
+        if point_clouds is not None or model.n_pc_sets:
+            model._check_point_clouds(point_clouds, img.shape[0])
+        self.point_clouds = point_clouds
+        if point_clouds is not None:
+            self._vkw["point_clouds"] = point_clouds
         self.t5_pf = (txt_next is not None and txt is not None
                       and getattr(model, "t5", None) is not None)
         self.txt_next = txt_next
@@ -122,7 +129,8 @@ class DDPStep:
         self.bounds = model.stage_bounds(stages) if self.distributed else [model.cfg.num_blocks, 0]
         self.S = len(self.bounds) - 1
         self.regions = model.grad_regions(self.bounds) if self.S > 1 else None
-        # the value tokenizer's embedding gradient (Octo.tail_region): declared after the heads
+        # the tail tokenizers' gradients (Octo.tail_region: the value tokenizer's embedding, the
+        # point-cloud tokenizer's parameters): declared after the heads
         # but final only after the last stage, so the staged form reduces it there
         self.tail = model.tail_region() if self.S > 1 else None
         if self.tail is not None and not model.store.region_trainable(*self.tail):

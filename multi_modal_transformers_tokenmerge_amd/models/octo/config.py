@@ -101,8 +101,26 @@ class OctoConfig:
     # with any of num_bins (2 .. 4096, default 256), mu (> 0, default 255.0, the reference's) and
     # encoding ("mu_law", the default, or "uniform"). None with Value sets present: the defaults
     value_tokenizer: Optional[dict] = None
+    # the point-cloud tokenizer behind the PointCloud{n} sets of input_sequence
+    # (tokenizers/pointclouds/point_cloud_tokenizer.py; YAML key tokenizers.pointclouds.encoder):
+    # a dict with num_points (P, the points of every cloud, n .. 4096; required) and any of
+    # num_neighbours_knn (1 .. 32, default 16), point_features (C, 3 .. 8, default 3) and hidden
+    # (the two LBR widths, each 32 / 64 / 128, default (64, 64)). Required with PointCloud sets
+    point_cloud_tokenizer: Optional[dict] = None
 
     def __post_init__(self):
+        if self.point_cloud_tokenizer is not None:
+            import re
+            from ...tokenizers.pointclouds.point_cloud_tokenizer import (
+                CONFIG_KEYS, check_point_cloud_config)
+            pc = self.point_cloud_tokenizer
+            if not isinstance(pc, dict) or set(pc) - set(CONFIG_KEYS) or "num_points" not in pc:
+                raise ValueError("point_cloud_tokenizer must be a dict with num_points and keys "
+                                 f"among {CONFIG_KEYS}, got {pc!r}")
+            sizes = [int(v) for v in re.findall(r"PointCloud\s*\{(\d+)\}", self.input_sequence)]
+            for n in sizes or [1]:
+                check_point_cloud_config(pc["num_points"], n, pc.get("num_neighbours_knn", 16),
+                                         pc.get("point_features", 3), pc.get("hidden", (64, 64)))
         if self.value_tokenizer is not None:
             from ...tokenizers.numeric_values.value_tokenizer import check_value_config
             vt = self.value_tokenizer
@@ -198,6 +216,14 @@ PRESETS = {
         input_sequence="[TaskDescriptionPrefix{32}] [Image{256};Value{8};Readout{4}]",
         token_compression_sequence="[TaskDescriptionPrefix{0}] [Image{16};Value{0};Readout{0}]",
         value_tokenizer=dict(num_bins=256, mu=255.0, encoding="mu_law")),
+    # configs[2] with one depth-camera cloud of 1024 points per observation as 64 point-cloud
+    # tokens (farthest-point sampling + 16-NN grouping, never compressed)
+    "octo-small-tome16-pc64": OctoConfig(
+        name="octo-small-tome16-pc64",
+        input_sequence="[TaskDescriptionPrefix{32}] [Image{256};PointCloud{64};Readout{4}]",
+        token_compression_sequence="[TaskDescriptionPrefix{0}] [Image{16};PointCloud{0};Readout{0}]",
+        point_cloud_tokenizer=dict(num_points=1024, num_neighbours_knn=16, point_features=3,
+                                   hidden=(64, 64))),
 }
 
 

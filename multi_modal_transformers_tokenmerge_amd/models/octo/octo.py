@@ -6,7 +6,9 @@ create_octo_train_state :334-386).
 MI355X design of the step (SURVEY §3.1 call stack):
   tokenizers  : frozen T5 (bf16 GEMM/attention kernels) -> Dense(768->D) [build addition for D!=768];
                 image stem kernels; device-drawn patch positions; value tokens (proprioception:
-                mu-law bins -> a shared embedding table, tokenizers/numeric_values)
+                mu-law bins -> a shared embedding table, tokenizers/numeric_values); point-cloud
+                tokens (farthest-point sampling + kNN grouping -> a shared two-layer embedding
+                with a max over the neighbours, tokenizers/pointclouds)
   sequence    : ONE fused kernel writes the token sequence (text | image + row/col emb | readout
                 embedding) + the learned position embedding; the blockwise mask is a token-set
                 table evaluated inside the attention kernel, never an (B, H, L, L) tensor
@@ -49,10 +51,11 @@ from ...tokenizers.readout.readout import AddPositionEmbedding
 from ...tokenizers.text.t5_base import T5Tokenizer
 from ...tokenizers.token_compression import MergeSource
 from ...tokenizers.numeric_values.value_tokenizer import ValueTokenizer
-from ...tokenizers.token_sequencer import Image, Readout, Text, TokenSequence, Value
+from ...tokenizers.pointclouds.point_cloud_tokenizer import PointCloudTokenizer
+from ...tokenizers.token_sequencer import Image, PointCloud, Readout, Text, TokenSequence, Value
 from .config import OctoConfig, get_config
 
-KIND_TEXT, KIND_IMAGE, KIND_READOUT, KIND_VALUE = 0, 1, 2, 3
+KIND_TEXT, KIND_IMAGE, KIND_READOUT, KIND_VALUE, KIND_POINT = 0, 1, 2, 3, 4
 
 
 class Octo:
@@ -81,6 +84,16 @@ class Octo:
             if isinstance(ts, Value) and ts.tokens_compressed_per_layer:
                 raise ValueError("Value sets are never compressed: token_compression_sequence must "
                                  f"give them {{0}}, got {{{ts.tokens_compressed_per_layer}}}")
+        pc_sets = [ts for ts in sets0 if isinstance(ts, PointCloud)]
+        self.n_pc_sets = len(pc_sets)
+        self.pc_tokens = pc_sets[0].num_tokens if pc_sets else 0   # tokens per cloud
+        for ts in pc_sets:
+            if ts.tokens_compressed_per_layer:
+                raise ValueError("PointCloud sets are never compressed: token_compression_sequence "
+                                 f"must give them {{0}}, got {{{ts.tokens_compressed_per_layer}}}")
+            if ts.num_tokens != self.pc_tokens:
+                raise ValueError("every PointCloud set must hold the same number of tokens, got "
+                                 f"{[t.num_tokens for t in pc_sets]}")
         self.has_text = self.n_text > 0
         if self.has_text and cfg.text_tokens != self.n_text:
             raise ValueError("text_tokens must equal the text set sizes of input_sequence")
@@ -141,6 +154,20 @@ class Octo:
                 store, "ValueTokenizer_0", D)
         elif cfg.value_tokenizer is not None:
             raise ValueError("value_tokenizer is set but input_sequence has no Value set")
+        # point-cloud tokens: declared after the value tokenizer and only with PointCloud sets
+        self.point_cloud_tokenizer = None
+        self.pc_points = self.pc_features = 0
+        if self.n_pc_sets:
+            if cfg.point_cloud_tokenizer is None:
+                raise ValueError("input_sequence has PointCloud sets: set point_cloud_tokenizer "
+                                 "(num_points at least)")
+            pc = dict(cfg.point_cloud_tokenizer)
+            self.pc_points = int(pc.pop("num_points"))
+            self.point_cloud_tokenizer = PointCloudTokenizer(**pc).bind(
+                store, "PointCloudTokenizer_0", D)
+            self.pc_features = self.point_cloud_tokenizer.C
+        elif cfg.point_cloud_tokenizer is not None:
+            raise ValueError("point_cloud_tokenizer is set but input_sequence has no PointCloud set")
         store.materialize(self.device, seed)
         # MMT_DETERMINISTIC=1: bitwise-reproducible gradients (ParamStore.set_deterministic)
         if os.environ.get("MMT_DETERMINISTIC", "0") == "1" and torch.device(self.device).type == "cuda":
@@ -155,7 +182,7 @@ class Octo:
         cfg = self.cfg
         NP = self.image_tokenizer.num_patches
         row_src = []
-        ti = ii = ri = vi = 0
+        ti = ii = ri = vi = pi = 0
         for ts in self.seq.token_sequence:
             for j in range(ts.num_tokens):
                 if isinstance(ts, Text):
@@ -164,6 +191,8 @@ class Octo:
                     row_src.append((KIND_IMAGE << 24) | (ii * NP + j))
                 elif isinstance(ts, Value):   # rows the sequence assembly leaves to the tokenizer
                     row_src.append((KIND_VALUE << 24) | (vi + j))
+                elif isinstance(ts, PointCloud):   # likewise
+                    row_src.append((KIND_POINT << 24) | (pi + j))
                 else:
                     row_src.append((KIND_READOUT << 24) | (ri + j))
             if isinstance(ts, Text):
@@ -172,6 +201,8 @@ class Octo:
                 ii += 1
             elif isinstance(ts, Value):
                 vi += ts.num_tokens
+            elif isinstance(ts, PointCloud):
+                pi += ts.num_tokens
             else:
                 ri += ts.num_tokens
         self.row_src = torch.tensor(row_src, dtype=torch.int32, device=self.device)
@@ -179,6 +210,10 @@ class Octo:
         self.value_rows = torch.tensor([row for row, v in enumerate(row_src)
                                         if v >> 24 == KIND_VALUE], dtype=torch.int32,
                                        device=self.device)
+        # point-cloud token (set-major, centroid) -> sequence row
+        self.pc_rows = torch.tensor([row for row, v in enumerate(row_src)
+                                     if v >> 24 == KIND_POINT], dtype=torch.int32,
+                                    device=self.device)
         img_rows = np.zeros(ii * NP, np.int32)                 # image token -> sequence row
         for row, v in enumerate(row_src):
             if v >> 24 == KIND_IMAGE:
@@ -274,17 +309,47 @@ class Octo:
                              f"n) or ({B}, {self.n_values})")
         return values.reshape(B, self.n_values)
 
+    def _check_point_clouds(self, point_clouds, B: int, fps_start=None):
+        """The `point_clouds` argument checked, None for a model without PointCloud sets.
+        ValueError: point_clouds missing from a model with PointCloud sets, given to one without,
+        not an fp32 tensor on the model's device, or of a shape other than (B, n_sets, P, C);
+        fps_start not an int32 (B, n_sets) tensor on that device."""
+        if not self.n_pc_sets:
+            if point_clouds is not None or fps_start is not None:
+                raise ValueError("point_clouds given, but input_sequence has no PointCloud set")
+            return None
+        shape = (B, self.n_pc_sets, self.pc_points, self.pc_features)
+        if point_clouds is None:
+            raise ValueError(f"input_sequence has PointCloud sets: pass point_clouds, fp32 {shape}")
+        if not torch.is_tensor(point_clouds) or point_clouds.dtype != torch.float32:
+            raise ValueError("point_clouds must be an fp32 tensor")
+        if point_clouds.device.type != self.device.type:
+            raise ValueError(f"point_clouds must live on the model's device ({self.device.type})")
+        if tuple(point_clouds.shape) != shape:
+            raise ValueError(f"point_clouds {tuple(point_clouds.shape)}: expected {shape}")
+        if fps_start is not None and (
+                not torch.is_tensor(fps_start) or fps_start.dtype != torch.int32
+                or tuple(fps_start.shape) != shape[:2]
+                or fps_start.device.type != self.device.type):
+            raise ValueError(f"fps_start must be an int32 {shape[:2]} tensor on the model's device")
+        return point_clouds
+
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
-                          positions=None, tome=None, t5_out=None, values=None):
+                          positions=None, tome=None, t5_out=None, values=None, point_clouds=None,
+                          fps_start=None):
         """Reference :91-126. Returns the final sequence (B, L_final, D) and the saved state.
         t5_out: the frozen T5 encoder's output for text_tokens, computed ahead (DDPStep's
         cross-step T5 pipeline); None runs the encoder here. values: the numbers behind the
         Value sets, fp32 (B, n_sets, n) or (B, n_sets * n), expected in [-1, 1]
         (tokenizers/numeric_values/value_tokenizer.py); required with Value sets in
-        input_sequence, refused without."""
+        input_sequence, refused without. point_clouds: the clouds behind the PointCloud sets,
+        fp32 (B, n_sets, P, C) (tokenizers/pointclouds/point_cloud_tokenizer.py), required and
+        refused likewise; fps_start (tests): int32 (B, n_sets), the first sampled point of every
+        cloud instead of the step's own (train: drawn, eval: point 0)."""
         B = images.shape[0]
         D = self.D
         values = self._check_values(values, B)
+        point_clouds = self._check_point_clouds(point_clouds, B, fps_start)
         st: Dict = dict(B=B, train=train, rng=rng, sample_offset=sample_offset)
         txt, T = None, max(self.n_text, 1)
         if self.has_text:
@@ -309,6 +374,10 @@ class Octo:
         if values is not None:  # the rows of kind 3, which the assembly skipped
             st["val_tok"] = self.value_tokenizer.forward(values, self.value_rows,
                                                          self.pos_embed.data, x0)
+        if point_clouds is not None:  # the rows of kind 4
+            st["pc_sv"] = self.point_cloud_tokenizer.forward(
+                point_clouds, self.pc_tokens, self.pc_rows, self.pos_embed.data, x0, train, rng,
+                sample_offset, fps_start)
         ctxs = self.layer_ctxs(train, rng, sample_offset)
         if tome is not None:  # injected ToMe index triples (tests: the golden step fixtures)
             for c, idx in zip(ctxs, tome):
@@ -343,7 +412,7 @@ class Octo:
 
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
                                        sample_offset=0, inject: Optional[dict] = None, t5_out=None,
-                                       action_pad_mask=None, values=None):
+                                       action_pad_mask=None, values=None, point_clouds=None):
         """Reference :139-145. Returns (loss (1,) fp32 device tensor, saved state). inject (tests):
         positions (rt, ct), t, eps, tome (per block an (unm, src, dst) triple of int32 device
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
@@ -353,7 +422,8 @@ class Octo:
         which is normalised by the number of real components. With it, or with
         OctoConfig.n_diffusion_samples = K > 1 (K independent (t, eps) draws per sample; inject
         t (K, B) / eps (K, B, h a)), the head runs its fused multi-draw loss on the pooled readout
-        (DiffusionActionHead.loss_forward_multi). values: generate_readouts'."""
+        (DiffusionActionHead.loss_forward_multi). values, point_clouds: generate_readouts'
+        (inject fps_start: its fps_start)."""
         inject = inject or {}
         actions = self._chunk_flat(actions)
         multi = self.cfg.n_diffusion_samples > 1 or action_pad_mask is not None
@@ -365,7 +435,8 @@ class Octo:
                 raise ValueError("action_pad_mask and actions differ in batch size")
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         inject.get("positions"), inject.get("tome"), t5_out,
-                                        values=values)
+                                        values=values, point_clouds=point_clouds,
+                                        fps_start=inject.get("fps_start"))
         B = xL.shape[0]
         if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
             cat = None
@@ -400,16 +471,18 @@ class Octo:
         return chunk_flat(actions, h, self.cfg.action_space_dim)
 
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
-                                       sample_offset=0, train=True, values=None):
+                                       sample_offset=0, train=True, values=None,
+                                       point_clouds=None):
         """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
         pooling) -> OctoDenoise (diffusion.py:88-107)."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values)
+                                       values=values, point_clouds=point_clouds)
         return self.head.predict_denoise_term_mean(self._readout_pooled(xL), time, noisy_actions)
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
-                                 positions=None, sampler=None, values=None):
+                                 positions=None, sampler=None, values=None, point_clouds=None,
+                                 fps_start=None):
         """Reference :147-154: readouts (the reference's backbone always runs with
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
         the sampler (action_heads/diffusion.py:146-209): `sampler` (a SamplerSpec or a dict of its
@@ -417,7 +490,8 @@ class Octo:
         (B, action_space_dim), or (B, action_horizon, action_space_dim) with a horizon > 1 (z
         and the returned noise stay flat, (B, h a))."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions,
-                                       values=values)
+                                       values=values, point_clouds=point_clouds,
+                                       fps_start=fps_start)
         if self.pooling is not None:
             e = self._readout_pooled(xL)
         else:
@@ -467,11 +541,11 @@ class Octo:
         return head
 
     def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                                  values=None):
+                                  values=None, point_clouds=None):
         """Reference :158-165 -> (B, pred_horizon, A) fp32 ((B, 1, A) as the reference)."""
         h = self._need(self.continuous_head, "continuous")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values)
+                                       values=values, point_clouds=point_clouds)
         return h.forward(self._readout_mean(xL))
 
     @staticmethod
@@ -480,7 +554,7 @@ class Octo:
             raise ValueError("action_pad_mask must be a bool tensor")
 
     def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None, values=None):
+                        action_pad_mask=None, values=None, point_clouds=None):
         """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved).
         actions (B, pred_horizon, A) or flat; OctoConfig.continuous_loss picks the squared error
         or L1. action_pad_mask: bool, the actions' shape, True where a component is real: padded
@@ -489,40 +563,41 @@ class Octo:
         h = self._need(self.continuous_head, "continuous")
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                        values=values)
+                                        values=values, point_clouds=point_clouds)
         loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
     def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                              values=None):
+                              values=None, point_clouds=None):
         """Reference :178-185 -> (B, A, num_bins) fp32, (B, pred_horizon, A, num_bins) with a
         pred_horizon > 1."""
         h = self._need(self.categorical_head, "categorical")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values)
+                                       values=values, point_clouds=point_clouds)
         return h.forward(self._readout_group_means(xL))
 
     def predict_categorical_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                                   mode="argmax", temperature=1.0, values=None):
+                                   mode="argmax", temperature=1.0, values=None,
+                                   point_clouds=None):
         """The categorical head rolled out: logits (predict_action_logits) decoded to actions
         (B, pred_horizon, A) fp32 through bin_values, by argmax or (mode "sample") one draw per
         component from softmax(logits / temperature) keyed by rng and sample_offset
         (CategoricalActionHead.decode)."""
         h = self._need(self.categorical_head, "categorical")
         logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train,
-                                            values=values)
+                                            values=values, point_clouds=point_clouds)
         return h.decode(logits, rng, sample_offset, mode, temperature)[0]
 
     def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None, values=None):
+                        action_pad_mask=None, values=None, point_clouds=None):
         """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved).
         actions (B, pred_horizon, A) or flat. action_pad_mask: compute_l2_loss's; the loss is the
         mean of the cross entropy over the real components."""
         h = self._need(self.categorical_head, "categorical")
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                        values=values)
+                                        values=values, point_clouds=point_clouds)
         loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
@@ -573,11 +648,12 @@ class Octo:
         them. The backward runs blocks [j, nb) and the token / stem part only for j == 0 and not
         tokens_frozen; with j == nb the heads do not produce the sequence gradient at all. The
         value tokenizer's embedding is a token-level parameter like those before block 0, though
-        it is declared after the heads (Octo.__init__)."""
+        it is declared after the heads (Octo.__init__); so are the point-cloud tokenizer's
+        parameters."""
         nb = self.cfg.num_blocks
         off0 = self._block_offset(0)
         pre = "StackedEncoder1DBlock_0/Block_"
-        vpre = "ValueTokenizer_0/"
+        vpre = ("ValueTokenizer_0/", "PointCloudTokenizer_0/")
         tokens_frozen, j = True, nb
         for p in self.store.params:
             if p.frozen:
@@ -643,8 +719,9 @@ class Octo:
     def grad_regions(self, stages) -> List[tuple]:
         """Flat-gradient index ranges that are final after each backward stage (stage 0: the
         heads and the last blocks, declared last in the store; the last stage: the first blocks
-        and everything declared before them). `stages` as in stage_bounds. With Value sets and
-        more than one stage, stage 0's region ends where tail_region() starts."""
+        and everything declared before them). `stages` as in stage_bounds. With Value or
+        PointCloud sets and more than one stage, stage 0's region ends where tail_region()
+        starts."""
         b = self.stage_bounds(stages)
         n_stages = len(b) - 1
         off = [self._block_offset(j) for j in b]
@@ -658,12 +735,15 @@ class Octo:
         return regions
 
     def tail_region(self) -> Optional[tuple]:
-        """The flat-gradient range of the value tokenizer's embedding, None without Value sets:
+        """The flat-gradient range of the value tokenizer's embedding and the point-cloud
+        tokenizer's parameters (the tail tokenizers), None without Value and PointCloud sets:
         declared after the heads, but written by the token backward, so it is final only after
         the LAST stage (DDPStep all-reduces it there, beside that stage's own region)."""
-        if self.value_tokenizer is None:
-            return None
-        return self.value_tokenizer.embedding.offset, self.store.n
+        if self.value_tokenizer is not None:
+            return self.value_tokenizer.embedding.offset, self.store.n
+        if self.point_cloud_tokenizer is not None:
+            return self.point_cloud_tokenizer.first_offset, self.store.n
+        return None
 
     def backward_stage(self, st: Dict, stage: int, stages):
         """Stage `stage` of a backward split as stage_bounds(stages) (the heads run in stage 0,
@@ -763,6 +843,8 @@ class Octo:
         K.colsum(dx0.view(B, self.L0 * D), self.pos_embed.grad.view(-1))
         if self.value_tokenizer is not None:
             self.value_tokenizer.backward(dx0, st["val_tok"], self.value_rows)
+        if self.point_cloud_tokenizer is not None:
+            self.point_cloud_tokenizer.backward(dx0, st["pc_sv"], self.pc_rows)
         it.backward(dimg, st["img_sv"])
         if self.text_proj is not None:
             self.text_proj.bwd(dtxt.view(B * T, D), st["t5_out"].view(B * T, -1), need_dx=False)
@@ -1105,38 +1187,41 @@ def _train_step(loss_fn, model: Octo, train_state: OCTOTrainState, text_tokens, 
     return train_state, grads_tree(model)
 
 
-def _step_kw(action_pad_mask, values) -> dict:
+def _step_kw(action_pad_mask, values, point_clouds=None) -> dict:
     """The optional keywords of a loss, passed only when given."""
     kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
     if values is not None:
         kw["values"] = values
+    if point_clouds is not None:
+        kw["point_clouds"] = point_clouds
     return kw
 
 
 def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                          action_pad_mask=None, values=None):
+                          action_pad_mask=None, values=None, point_clouds=None):
     """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
     metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_l2_loss's."""
-    kw = _step_kw(action_pad_mask, values)
+    kw = _step_kw(action_pad_mask, values, point_clouds)
     return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                           action_pad_mask=None, values=None):
+                           action_pad_mask=None, values=None, point_clouds=None):
     """Reference octo.py:282-320: value_and_grad of mean(compute_ce_loss), apply_gradients,
     metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_ce_loss's."""
-    kw = _step_kw(action_pad_mask, values)
+    kw = _step_kw(action_pad_mask, values, point_clouds)
     return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                         inject: Optional[dict] = None, action_pad_mask=None, values=None):
+                         inject: Optional[dict] = None, action_pad_mask=None, values=None,
+                         point_clouds=None):
     """Reference octo.py:204-240: value_and_grad of the denoise loss, apply_gradients, metrics
     merge. Returns (train_state, grads) like the reference; grads are views of the flat gradient
     buffer by parameter name, the loss is train_state.last_loss (device) and the running average
     train_state.metrics. action_pad_mask, values: compute_diffusion_denoise_loss's."""
-    kw = _step_kw(action_pad_mask, values)
+    kw = _step_kw(action_pad_mask, values, point_clouds)
     return _train_step(model.compute_diffusion_denoise_loss, model, train_state, text_tokens,
                        images, actions, inject=inject, **kw)

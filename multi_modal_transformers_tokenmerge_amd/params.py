@@ -65,6 +65,19 @@ def normal(std):
     return init
 
 
+def xavier_uniform(flax_shape):
+    """variance_scaling(1.0, 'fan_avg', 'uniform') on the Flax kernel shape: U(-a, a) with
+    a = sqrt(6 / (fan_in + fan_out))."""
+    fan_in, fan_out = _fans(flax_shape)
+    a = math.sqrt(6.0 / (fan_in + fan_out))
+
+    def init(t: torch.Tensor, g: torch.Generator):
+        with torch.no_grad():
+            t.copy_((torch.rand(t.shape, generator=g) * 2.0 - 1.0) * a)
+        return t
+    return init
+
+
 def variance_scaling_normal(scale, flax_shape):
     fan_in, _ = _fans(flax_shape)
     return normal(math.sqrt(scale / fan_in))

@@ -2,7 +2,8 @@
 ``multi_modal_transformers/tokenizers/token_sequencer.py`` (TokenSet :20-52, Text :55-91,
 TaskDescriptionPrefix :94-113, Image :116-148, Readout :151-183, TokenSequence :186-340), plus a
 fourth class the reference's grammar lacks: Value, the tokens of low-dimensional numbers
-(tokenizers/numeric_values/value_tokenizer.py), with Image's rules.
+(tokenizers/numeric_values/value_tokenizer.py), and a fifth: PointCloud, the sampled centroids of
+a point cloud (tokenizers/pointclouds/point_cloud_tokenizer.py), both with Image's rules.
 
 The reference materialises the (H, L, L) boolean mask with Python loops on every apply
 (:313-321). Here that dense form exists for API parity and tests only; the hot path consumes the
@@ -116,6 +117,21 @@ class Value(TokenSet):
         return "ones"
 
 
+class PointCloud(TokenSet):
+    """Point-cloud tokens (one sampled centroid with its neighbourhood each;
+    tokenizers/pointclouds/point_cloud_tokenizer.py), Image's rules: the PointCloud sets of its
+    own timestep + every non-readout set with t' <= t. Never compressed."""
+    modality = "pointclouds"
+
+    def inter_kind(self, other):
+        if isinstance(other, Readout):
+            return "zeros"
+        return "ones" if other.timestep <= self.timestep else "zeros"
+
+    def intra_kind(self):
+        return "ones"
+
+
 class Readout(TokenSet):
     """Reference :151-183: own set + every non-readout set with t' <= t."""
     modality = "readouts"
@@ -130,7 +146,7 @@ class Readout(TokenSet):
 
 
 _CLASSES = {"Text": Text, "TaskDescriptionPrefix": TaskDescriptionPrefix, "Image": Image,
-            "Value": Value, "Readout": Readout}
+            "Value": Value, "PointCloud": PointCloud, "Readout": Readout}
 
 
 @dataclass
@@ -140,6 +156,7 @@ class TokenEmbeddings:
     images: object = None
     readouts: object = None
     values: object = None
+    pointclouds: object = None
 
 
 @dataclass
@@ -204,7 +221,7 @@ class TokenSequence:
 
     # ------------------------------------------------------------------ slices (:272-304)
     def _generate_embedding_slices(self):
-        idx = {"images": 0, "text": 0, "readouts": 0, "values": 0}
+        idx = {"images": 0, "text": 0, "readouts": 0, "values": 0, "pointclouds": 0}
         out = []
         for ts in self.token_sequence:
             out.append((idx[ts.modality], ts.num_tokens))
