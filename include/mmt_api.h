@@ -108,6 +108,34 @@ int mmt_tome_match(const void* metric, int dtype, int n, int t, int heads, int c
                    int64_t s_t, int64_t s_h, int r, int flags, int32_t* unm_idx, int32_t* src_idx,
                    int32_t* dst_idx, float* node_max, void* workspace, int64_t ws_bytes,
                    mmt_stream_t stream);
+/* The kernel chain that the last mmt_tome_match call launched: MMT_TOME_ROUTE_NONE after a call
+ * rejected before any launch, else the form in MMT_TOME_ROUTE_FORM_MASK —
+ *   _FUSED       one launch (norm + score + rank in LDS): 16-B-vector metric, the MFMA path and
+ *                both normalised halves within 160 KB of LDS (t <= 513 at c = 64);
+ *   _BIG_AG1/2   norm, the b-resident score kernel with 1 / 2 a tiles per workgroup, rank8: the
+ *                MFMA path, c % 4 == 0 and the b half within 160 KB (t <= 1153 at c = 64); two a
+ *                tiles when n * ceil(ta / 32) > 256 and they still fit;
+ *   _TILED_MFMA  norm, the tiled score kernel (MFMA: the MFMA path and even c), rank;
+ *   _TILED_VALU  the same with the VALU fmaf chain —
+ * with MMT_TOME_ROUTE_NORM_SCALAR when the norm was the scalar kernel (c % 8 != 0, or a base or
+ * stride that is no multiple of 16 B), else MMT_TOME_ROUTE_LPR = the lanes per token row of the
+ * vector norm / the fused kernel (the power of two >= c / 8); MMT_TOME_ROUTE_NBT = the b tiles per
+ * LDS group of the tiled forms (1..4, 0 otherwise); MMT_TOME_ROUTE_IN_BF16 for a bf16 metric.
+ * Process-wide, not thread-safe. */
+enum {
+  MMT_TOME_ROUTE_NONE = 0,
+  MMT_TOME_ROUTE_FUSED = 1,
+  MMT_TOME_ROUTE_BIG_AG1 = 2,
+  MMT_TOME_ROUTE_BIG_AG2 = 3,
+  MMT_TOME_ROUTE_TILED_MFMA = 4,
+  MMT_TOME_ROUTE_TILED_VALU = 5,
+  MMT_TOME_ROUTE_FORM_MASK = 0xff,
+  MMT_TOME_ROUTE_NORM_SCALAR = 0x10000,
+  MMT_TOME_ROUTE_IN_BF16 = 0x20000
+};
+#define MMT_TOME_ROUTE_LPR(route) (((route) >> 8) & 0xff)
+#define MMT_TOME_ROUTE_NBT(route) (((route) >> 20) & 0xf)
+int mmt_tome_last_route(void);
 
 /* mmt_tome_merge_wavg_fwd replaces token_compression.py:114-129 (merge_wavg) applied with the
  * merge closure of :90-109 (mode "sum"), fused with the surrounding sequence copy:

@@ -47,6 +47,7 @@ SIGNATURES: dict[str, list] = {
     "mmt_attn_last_route": [],
     "mmt_norm_last_route": [],
     "mmt_stem_last_route": [],
+    "mmt_tome_last_route": [],
     "mmt_set_deterministic": [P, P, L],
     "mmt_det_flush": [P, P, L, P],
     "mmt_gemm_colsum_rows": [I, I, I, I, I, I, I],
@@ -144,6 +145,7 @@ _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: erro
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
             "mmt_norm_last_route": I,     # returns a NORM_ROUTE_* value
             "mmt_stem_last_route": I,     # returns a STEM_ROUTE_* value
+            "mmt_tome_last_route": I,     # returns a TOME_ROUTE_* value
             "mmt_sampler_last_route": I,  # returns a SAMPLER_ROUTE_* value
             "mmt_diffusion_loss_last_route": I,  # returns a DIFFUSION_LOSS_ROUTE_* value
             "mmt_stem_conv_wgrad_slabs": I}
@@ -285,6 +287,24 @@ def stem_route(entry: int, form: int = 0, in_u8: bool = False) -> int:
 
 def stem_last_route() -> int:
     return call("mmt_stem_last_route")
+
+
+# MMT_TOME_ROUTE_* (include/mmt_api.h): what mmt_tome_last_route() reports
+(TOME_ROUTE_NONE, TOME_ROUTE_FUSED, TOME_ROUTE_BIG_AG1, TOME_ROUTE_BIG_AG2, TOME_ROUTE_TILED_MFMA,
+ TOME_ROUTE_TILED_VALU) = range(6)
+TOME_ROUTE_FORM_MASK, TOME_ROUTE_NORM_SCALAR, TOME_ROUTE_IN_BF16 = 0xff, 0x10000, 0x20000
+
+
+def tome_route(form: int, lpr: int = 0, nbt: int = 0, in_bf16: bool = False) -> int:
+    """The route of the mmt_tome_match chain `form` with `lpr` lanes per token row in the vector
+    norm / fused kernel (MMT_TOME_ROUTE_LPR; 0: the scalar norm), `nbt` b tiles per LDS group of
+    the tiled forms (MMT_TOME_ROUTE_NBT; 0 otherwise) and the metric's type."""
+    return (form | lpr << 8 | nbt << 20 | (0 if lpr else TOME_ROUTE_NORM_SCALAR)
+            | (TOME_ROUTE_IN_BF16 if in_bf16 else 0))
+
+
+def tome_last_route() -> int:
+    return call("mmt_tome_last_route")
 
 
 # MMT_SAMPLER_ROUTE_* (include/mmt_api.h): what mmt_sampler_last_route() reports

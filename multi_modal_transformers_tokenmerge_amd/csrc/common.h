@@ -149,6 +149,16 @@ extern int g_stem_route;
 inline int stem_route(int entry, int form, bool in_u8) {
   return entry | form << 8 | (in_u8 ? MMT_STEM_ROUTE_IN_U8 : 0);
 }
+// The kernel chain of the last mmt_tome_match (MMT_TOME_ROUTE_*, include/mmt_api.h;
+// mmt_tome_last_route): set next to each launch chain of tome.hip, MMT_TOME_ROUTE_NONE after a
+// call rejected before its launch. Defined in core.hip. Process-wide, not thread-safe.
+// lpr: lanes per token row of the vector norm / fused kernel (0: the scalar norm); nbt: b tiles
+// per LDS group of the tiled forms (0 otherwise).
+extern int g_tome_route;
+inline int tome_route(int form, int lpr, int nbt, bool in_bf16) {
+  return form | lpr << 8 | nbt << 20 | (lpr ? 0 : MMT_TOME_ROUTE_NORM_SCALAR) |
+         (in_bf16 ? MMT_TOME_ROUTE_IN_BF16 : 0);
+}
 // base pointer of an operand moved as `bytes`-wide vectors (a power of two)
 inline bool aligned_to(const void* p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 

@@ -36,6 +36,9 @@ extern "C" int mmt_norm_last_route(void) { return mmt::g_norm_route; }
 // the kernel form of the last image-stem launch (common.h; set by stem.hip)
 int mmt::g_stem_route = MMT_STEM_ROUTE_NONE;
 extern "C" int mmt_stem_last_route(void) { return mmt::g_stem_route; }
+// the kernel chain of the last mmt_tome_match (common.h; set by tome.hip)
+int mmt::g_tome_route = MMT_TOME_ROUTE_NONE;
+extern "C" int mmt_tome_last_route(void) { return mmt::g_tome_route; }
 
 extern "C" int mmt_device_status(mmt_stream_t stream) {
   unsigned int* w = mmt::fault_word();

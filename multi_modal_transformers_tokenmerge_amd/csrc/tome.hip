@@ -910,6 +910,7 @@ extern "C" int mmt_tome_match(const void* metric, int dtype, int n, int t, int h
                               int32_t* unm_idx, int32_t* src_idx, int32_t* dst_idx,
                               float* node_max, void* workspace, int64_t ws_bytes,
                               mmt_stream_t stream) {
+  g_tome_route = MMT_TOME_ROUTE_NONE;  // a call rejected before its launch reports no kernel
   MMT_CHECK_ARG(metric && (unm_idx || (t + 1) / 2 == r) && src_idx && dst_idx && workspace,
                 "mmt_tome_match: null pointer");  // unm may be NULL when every A token merges
   MMT_CHECK_ARG(n > 0 && t >= 2 && heads >= 1 && c >= 1, "mmt_tome_match: bad shape n=%d t=%d", n, t);
@@ -934,9 +935,11 @@ extern "C" int mmt_tome_match(const void* metric, int dtype, int n, int t, int h
   const bool vec = (c % 8 == 0) && (s_n % vw == 0) && (s_t % vw == 0) && (s_h % vw == 0) &&
                    ((uintptr_t)metric % 16 == 0);
   const size_t fused_lds = fused_match_lds(t, c);
+  const bool bf16_in = dtype == MMT_BF16;
   if (vec && g_match_use_mfma && fused_lds <= 160 * 1024 && c / 8 <= 64) {
     // one launch: norm + score + rank with both halves in LDS
     const int lpr = pow2_at_least(c / 8);
+    g_tome_route = tome_route(MMT_TOME_ROUTE_FUSED, lpr, 0, bf16_in);
 #define FUSED(T, LPR)                                                                            \
   do {                                                                                           \
     static const bool attr_ = (hipFuncSetAttribute((const void*)tome_match_fused_kernel<T, LPR>, \
@@ -964,8 +967,9 @@ extern "C" int mmt_tome_match(const void* metric, int dtype, int n, int t, int h
   }
   // 1. per-token head sum + L2 normalisation
   const int64_t rows = (int64_t)n * t;
+  const int norm_lpr = vec ? pow2_at_least(c / 8) : 0;  // 0: the scalar norm
   if (vec) {
-    const int lpr = pow2_at_least(c / 8);
+    const int lpr = norm_lpr;
 #define NORMV(T, LPR)                                                                          \
   hipLaunchKernelGGL((tome_norm_vec_kernel<T, LPR>), dim3((rows * LPR + NORM_NT - 1) / NORM_NT), \
                      dim3(NORM_NT), 0, s, (const T*)metric, n, t, heads, c, s_n, s_t, s_h, An, Bn)
@@ -998,6 +1002,8 @@ extern "C" int mmt_tome_match(const void* metric, int dtype, int n, int t, int h
   if (g_match_use_mfma && c % 4 == 0 && score_big_lds(t, c, 1) <= 160 * 1024) {
     const bool two = (int64_t)n * n_at > 256 && score_big_lds(t, c, 2) <= 160 * 1024;
     const int wps = two ? (n_at + 1) / 2 : n_at;
+    g_tome_route = tome_route(two ? MMT_TOME_ROUTE_BIG_AG2 : MMT_TOME_ROUTE_BIG_AG1, norm_lpr, 0,
+                              bf16_in);
 #define SBIG(AG)                                                                                  \
   do {                                                                                            \
     static const bool attr_ = (hipFuncSetAttribute((const void*)tome_score_big_kernel<AG>,       \
@@ -1023,6 +1029,8 @@ extern "C" int mmt_tome_match(const void* metric, int dtype, int n, int t, int h
   const size_t smem = fixed + nbt * tile;
   const bool mfma = g_match_use_mfma && (c % 2 == 0);
   const dim3 sgrid((ta + 31) / 32, n);
+  g_tome_route = tome_route(mfma ? MMT_TOME_ROUTE_TILED_MFMA : MMT_TOME_ROUTE_TILED_VALU, norm_lpr,
+                            nbt, bf16_in);
 #define SCORE(M)                                                                              \
   do {                                                                                        \
     static const bool attr_ = (hipFuncSetAttribute((const void*)tome_score_kernel<M>,        \
