@@ -842,6 +842,42 @@ int mmt_pc_embed_bwd(const void* dx0, int64_t xs_b, int64_t xs_t, const int32_t*
                      float* dw2, float* db2, float* dw_out, float* db_out, void* workspace,
                      int64_t workspace_bytes, mmt_stream_t stream);
 
+/* ------------------------------------------------------------------ QK-norm
+ * flax.linen.SelfAttention(normalize_qk=True): LayerNorm(use_bias=False) over the head dimension of
+ * the projected queries and keys before the dot product (`query_ln`, `key_ln`; the reference's
+ * attention_blocks/compressed_attention.py:184-198), csrc/qknorm.hip. qkv: n_tokens rows of the
+ * packed (3, H, Dh) projection, dtype MMT_F32 or MMT_BF16, row stride ld >= 3 H Dh elements, every
+ * row 16-B aligned. For every token and head, for q and k separately, in fp32 over the Dh elements
+ * x of the head row:
+ *   mu = mean(x), var = max(0, mean(x^2) - mu^2)       Flax's fast variance
+ *   y  = (x - mu) * rsqrt(var + eps) * scale           scale = q_scale (Dh) for q, k_scale for k
+ * The two means are accumulated on x - x[0], which leaves var and x - mu as they are in exact
+ * arithmetic and keeps the row's offset out of the fp32 cancellation; a constant row gives y = 0.
+ * Forward: y overwrites q and k in place; the V third and the columns past 3 H Dh are neither read
+ * nor written. qk_pre (n_tokens, 2 H Dh) contiguous, the dtype of qkv, or NULL (evaluation): the
+ * pre-norm q and k, bit for bit, for the backward.
+ * Checked before a launch (MMT_ERR_INVALID): null pointers; a dtype that is neither code; Dh not in
+ * {32, 64, 128, 256}; n_tokens or H <= 0; ld < 3 H Dh; qkv (or qk_pre, workspace) not 16-B aligned
+ * or ld not a whole number of 16-B vectors; eps < 0 or NaN. */
+int mmt_qk_norm_fwd(void* qkv, int dtype, int64_t ld, int64_t n_tokens, int H, int Dh,
+                    const float* q_scale, const float* k_scale, float eps, void* qk_pre,
+                    mmt_stream_t stream);
+/* Backward, in place on the q and k thirds of dqkv (the attention backward's output, the layout
+ * and dtype rules of qkv; the V third keeps its bits): with the statistics recomputed from qk_pre,
+ * xhat = (x - mu) rs, g = dy * scale,
+ *   dx = rs * (g - mean(g) - xhat * mean(g * xhat))
+ * and dq_scale[j] += sum over (token, head) of dy[j] * xhat[j] (dk_scale likewise), fp32 (Dh). The
+ * sums are ordered: every workgroup of a grid that depends on (n_tokens, H, Dh) alone writes one
+ * partial row per column to the workspace, and one wave per column adds the partial rows in a
+ * fixed order and then adds the total ONCE to the gradient: one writer per element, no float
+ * atomics, bitwise reproducible with and without the deterministic mode.
+ * workspace: >= mmt_qk_norm_bwd_workspace(n_tokens, H, Dh) bytes (at most 2 MiB), 16-B aligned. */
+int64_t mmt_qk_norm_bwd_workspace(int64_t n_tokens, int H, int Dh);
+int mmt_qk_norm_bwd(void* dqkv, int dtype, int64_t ld, int64_t n_tokens, int H, int Dh,
+                    const void* qk_pre, const float* q_scale, const float* k_scale, float eps,
+                    float* dq_scale, float* dk_scale, void* workspace, int64_t workspace_bytes,
+                    mmt_stream_t stream);
+
 /* ------------------------------------------------------------------ attention pooling
  * MultiHeadAttentionPooling (attention_blocks/attention.py:122-150) of the readout tokens, the
  * pieces around its GEMMs (csrc/pool.hip). None of them accumulates across workgroups (no

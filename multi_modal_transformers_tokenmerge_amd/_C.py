@@ -94,6 +94,9 @@ SIGNATURES: dict[str, list] = {
     "mmt_pc_embed_bwd_workspace": [I, I, I, I, I, I, I],
     "mmt_pc_embed_bwd": [P, L, L, P, I, P, L, L, I, I, I, I, I, I, P, P, P, I, I, P, P, P, P, P, P, P,
                          P, P, P, P, P, L, P],
+    "mmt_qk_norm_fwd": [P, I, L, L, I, I, P, P, F, P, P],
+    "mmt_qk_norm_bwd_workspace": [L, I, I],
+    "mmt_qk_norm_bwd": [P, I, L, L, I, I, P, P, P, F, P, P, P, L, P],
     "mmt_patch_embed_grad": [I, I, I, I, I, I, I, P, P, P, P, P, P, P],
     "mmt_stem_conv_pool": [P, I, I, I, P, P, P, P, P],
     "mmt_stem_conv_wgrad_slabs": [I, I, I],
@@ -140,6 +143,7 @@ SIGNATURES: dict[str, list] = {
 _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)
             "mmt_pc_embed_bwd_workspace": L,  # returns a byte count (negative: error)
+            "mmt_qk_norm_bwd_workspace": L,   # returns a byte count (negative: error)
             "mmt_gemm_colsum_rows": I,    # returns a row count
             "mmt_gemm_last_route": I,     # returns a ROUTE_* value
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
@@ -346,6 +350,7 @@ VALUE_MIN_BINS, VALUE_MAX_BINS = 2, 4096
 PC_MAX_POINTS, PC_MAX_TOKENS, PC_MAX_NEIGHBOURS = 4096, 256, 32
 PC_MIN_FEATURES, PC_MAX_FEATURES, PC_MAX_WIDTH = 3, 8, 4096
 PC_HIDDEN_WIDTHS = (32, 64, 128)
+QK_NORM_WIDTHS = (32, 64, 128, 256)   # head widths of mmt_qk_norm_fwd / _bwd
 HEAD_LOSS_MSE, HEAD_LOSS_L1 = 0, 1   # MMT_HEAD_LOSS_* (mmt_head_continuous loss_kind)
 DECODE_ARGMAX, DECODE_SAMPLE = 0, 1  # MMT_DECODE_* (mmt_head_categorical_decode mode)
 

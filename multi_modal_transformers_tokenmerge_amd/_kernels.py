@@ -1283,3 +1283,63 @@ def pc_embed_bwd(dx0, rows, points, cidx, nidx, argmax, w1, b1, w2, b2, w_out, g
             ptr(b1), ptr(w2), ptr(b2), ptr(w_out), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2),
             ptr(dw_out), ptr(db_out), ptr(ws), nbytes, _C.stream_ptr())
     return grads
+
+
+# ------------------------------------------------------------------------------------------ QK-norm
+QK_NORM_WIDTHS = _C.QK_NORM_WIDTHS
+
+
+def _qk_norm_args(qkv: torch.Tensor, H: int, Dh: int, q_scale, k_scale, what: str):
+    """(n_tokens, dtype code, ld) of a packed (rows, >= 3 H Dh) or (B, L, >= 3 H Dh) buffer with
+    unit inner stride and one row stride. The library checks the rest (Dh, ld, alignment, dtype:
+    MMTError); scales that are not contiguous fp32 (Dh,) are an MMTError here, before any launch."""
+    if qkv.dim() == 3 and (qkv.shape[0] == 1 or qkv.stride(0) == qkv.shape[1] * qkv.stride(1)):
+        N, ld = qkv.shape[0] * qkv.shape[1], qkv.stride(1)
+    elif qkv.dim() == 2:
+        N, ld = qkv.shape[0], qkv.stride(0)
+    else:
+        raise ValueError(f"{what} must be (rows, 3 H Dh) or (B, L, 3 H Dh) with one row stride")
+    W = qkv.shape[-1]
+    if (W > 1 and qkv.stride(-1) != 1) or N < 1:
+        raise ValueError(f"{what} must have unit inner stride and at least one row")
+    if N == 1 or W < 3 * H * Dh:   # a buffer narrower than 3 H Dh: the library rejects its ld
+        ld = W
+    for s, name in ((q_scale, "q_scale"), (k_scale, "k_scale")):
+        if s.dtype != torch.float32 or tuple(s.shape) != (Dh,) or not s.is_contiguous():
+            raise _C.MMTError(f"{what}: {name} must be contiguous fp32 ({Dh},), got {s.dtype} "
+                              f"{tuple(s.shape)}")
+    return N, DT.get(qkv.dtype, -1), ld
+
+
+def qk_norm_fwd(qkv: torch.Tensor, H: int, Dh: int, q_scale: torch.Tensor, k_scale: torch.Tensor,
+                eps: float = 1e-6, save: bool = True):
+    """LayerNorm(use_bias=False) over the head dimension of the q and k thirds of the packed qkv
+    (rows, 3 H Dh) / (B, L, 3 H Dh) fp32 or bf16 buffer, in place (mmt_qk_norm_fwd); the V third is
+    untouched. Returns qk_pre (rows, 2 H Dh), the pre-norm q and k for qk_norm_bwd (None with
+    save=False: an evaluation-only forward)."""
+    _dev(qkv, q_scale, k_scale)
+    N, code, ld = _qk_norm_args(qkv, H, Dh, q_scale, k_scale, "qk_norm_fwd")
+    pre = torch.empty((N, 2 * H * Dh), dtype=qkv.dtype, device=qkv.device) if save else None
+    _C.call("mmt_qk_norm_fwd", ptr(qkv), code, ld, N, H, Dh, ptr(q_scale), ptr(k_scale), float(eps),
+            ptr(pre), _C.stream_ptr())
+    return pre
+
+
+def qk_norm_bwd(dqkv: torch.Tensor, qk_pre: torch.Tensor, H: int, Dh: int, q_scale: torch.Tensor,
+                k_scale: torch.Tensor, dq_scale: torch.Tensor, dk_scale: torch.Tensor,
+                eps: float = 1e-6) -> torch.Tensor:
+    """dqkv (the layout of qkv): its q and k thirds become the gradient of the pre-norm q and k,
+    in place; dq_scale / dk_scale (Dh,) fp32 += the scale gradients, ordered sums without atomics
+    (mmt_qk_norm_bwd). Returns dqkv."""
+    _dev(dqkv, qk_pre, q_scale, k_scale, dq_scale, dk_scale)
+    N, code, ld = _qk_norm_args(dqkv, H, Dh, q_scale, k_scale, "qk_norm_bwd")
+    _qk_norm_args(dqkv, H, Dh, dq_scale, dk_scale, "qk_norm_bwd (gradients)")
+    if qk_pre.dtype != dqkv.dtype or tuple(qk_pre.shape) != (N, 2 * H * Dh) or \
+            not qk_pre.is_contiguous():
+        raise ValueError(f"qk_pre must be contiguous {dqkv.dtype} {(N, 2 * H * Dh)}")
+    nbytes = _C.call("mmt_qk_norm_bwd_workspace", N, H, Dh)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dqkv.device)
+    _C.call("mmt_qk_norm_bwd", ptr(dqkv), code, ld, N, H, Dh, ptr(qk_pre), ptr(q_scale),
+            ptr(k_scale), float(eps), ptr(dq_scale), ptr(dk_scale), ptr(ws), nbytes,
+            _C.stream_ptr())
+    return dqkv

@@ -377,8 +377,9 @@ class Encoder1DBlock(Bindable):
     the reference's config nodes: flax.linen.LayerNorm (epsilon; reduction over the SEQUENCE
     axis, reduction_axes [1], vanilla_decoder.yaml:5-13), flax.linen.Dropout (rate),
     flax.linen.SelfAttention (num_heads, qkv_features = the input width, dropout_rate,
-    kernel_init, bias_init) and an MLPBlock node (or MLPBlock). ``__call__(inputs, mask=None,
-    train=None) -> (x, None)`` as the reference (train / mask from the constructor or the call,
+    kernel_init, bias_init, normalize_qk: LayerNorm(use_bias=False) over the head dimension of the
+    projected q and k, parameters query_ln/scale and key_ln/scale) and an MLPBlock node (or
+    MLPBlock). ``__call__(inputs, mask=None, train=None) -> (x, None)`` as the reference (train / mask from the constructor or the call,
     flax merge_param); the dense mask is converted to the token-set table the kernels evaluate
     (token_sequencer.sets_from_mask). Differentiable through torch autograd: the backward runs
     the block's explicit backward kernels and accumulates the parameter gradients in the store's
@@ -407,17 +408,26 @@ class Encoder1DBlock(Bindable):
         self.rate = float(sget(self.dropout, "rate", 0.0))
         self.H = int(sget(self.self_attention, "num_heads", 1))
         self.attn_rate = float(sget(self.self_attention, "dropout_rate", 0.0))
+        # flax.linen.SelfAttention.normalize_qk: LayerNorm(use_bias=False) over the head dimension
+        # of the projected q and k (query_ln / key_ln, flax's default epsilon 1e-6)
+        self.normalize_qk = bool(sget(self.self_attention, "normalize_qk", False))
+        self.q_ln = self.k_ln = None
+
+    QK_LN_EPS = 1e-6
 
     @classmethod
     def create(cls, store: ParamStore, name: str, D: int, num_heads: int, mlp_dim: int,
                eps: float = 1e-6, dropout_rate: float = 0.1, attn_dropout_rate: float = 0.1,
-               fp8: bool = False, fp8_residual: bool = False) -> "Encoder1DBlock":
+               fp8: bool = False, fp8_residual: bool = False,
+               normalize_qk: bool = False) -> "Encoder1DBlock":
         """The block from its dimensions, declared in ``store`` (the Octo model's path)."""
+        sa_kw = {"normalize_qk": True} if normalize_qk else {}
         blk = cls(LayerSpec("flax.linen.LayerNorm", {"epsilon": eps, "reduction_axes": [1],
                                                      "feature_axes": [-1]}),
                   LayerSpec("flax.linen.Dropout", {"rate": dropout_rate}),
                   LayerSpec("flax.linen.SelfAttention", {"num_heads": num_heads, "qkv_features": D,
-                                                         "dropout_rate": attn_dropout_rate}),
+                                                         "dropout_rate": attn_dropout_rate,
+                                                         **sa_kw}),
                   MLPBlock(LayerSpec("flax.linen.Dense", {"features": mlp_dim}),
                            LayerSpec("flax.linen.relu", partial=True),
                            LayerSpec("flax.linen.Dropout", {"rate": dropout_rate}),
@@ -440,6 +450,12 @@ class Encoder1DBlock(Bindable):
                          bias_init=binit, fp8=self.fp8)
         self.out = Dense(store, f"{name}/SelfAttention_0/out", D, D, kernel_init=kinit(),
                          bias_init=binit, fp8=self.fp8 and self.fp8_residual)
+        if self.normalize_qk:
+            if self.Dh not in K.QK_NORM_WIDTHS:
+                raise ValueError(f"normalize_qk: head width {self.Dh} not among "
+                                 f"{K.QK_NORM_WIDTHS} (mmt_qk_norm_fwd)")
+            self.q_ln = store.add(f"{name}/SelfAttention_0/query_ln/scale", (self.Dh,), const(1.0))
+            self.k_ln = store.add(f"{name}/SelfAttention_0/key_ln/scale", (self.Dh,), const(1.0))
         self.ln1 = SeqLayerNorm(store, f"{name}/LayerNorm_1", D, self.eps)
         self.mlp.fp8, self.mlp.fp8_residual = self.fp8, self.fp8_residual
         self.mlp.bind(store, f"{name}/MLPBlock_0", D)
@@ -492,6 +508,11 @@ class Encoder1DBlock(Bindable):
         bits = None
         y0, mu0, rs0 = self.ln0.fwd(x)
         qkv = self.qkv.fwd(y0.view(B * L, D)).view(B, L, 3 * D)
+        qk_pre = None
+        if self.normalize_qk:
+            # in place on the q and k thirds, before every reader of qkv (attention, the ToMe
+            # metric, the pruning importance); the side stream's fork below follows this launch
+            qk_pre = K.qk_norm_fwd(qkv, H, Dh, self.q_ln.data, self.k_ln.data, self.QK_LN_EPS)
         tome_idx = None
         Mh = self.mlp.dense.out_f
 
@@ -601,7 +622,7 @@ class Encoder1DBlock(Bindable):
                                     **drop(DROP_MLP_OUT, L2, kpm))
         saved = dict(x=x, y0=y0, mu0=mu0, rs0=rs0, qkv=qkv, o=o, o_in=o_in, lse=lse, bits=bits,
                      x1=x1, y1=y1, mu1=mu1, rs1=rs1, h=h, hbits=hbits, tome=tome, prune=prune,
-                     kp=kp, kpm=kpm, kpa=kpa, kbias=kbias,
+                     kp=kp, kpm=kpm, kpa=kpa, kbias=kbias, qk_pre=qk_pre,
                      # every merge of the block in the order applied (one set: [tome]; several:
                      # the last set first, `tome` then None)
                      tome_sets=tome_sets)
@@ -661,10 +682,18 @@ class Encoder1DBlock(Bindable):
             do = K.topk_scatter_bwd(do.view(B, Lo, D), pidx, L)
             dx1 = K.topk_scatter_bwd(dx1.view(B, Lo, D), pidx, L)
         # the QKV bias gradient (column sums of dqkv) is accumulated inside the attention backward
+        # (without QK-norm)
+        qkn = self.normalize_qk
         dqkv = K.attn_bwd(sv["qkv"], sv["o"], do.view(B, L, D), sv["lse"], self.H, self.scale,
-                          ctx.table, sv["bits"], kpa, bias_grad=self.qkv.b.grad,
+                          ctx.table, sv["bits"], kpa, bias_grad=None if qkn else self.qkv.b.grad,
                           key_bias=sv.get("kbias"))
-        dy0 = self.qkv.bwd(dqkv.view(B * L, 3 * D), sv["y0"].view(B * L, D), bias_grad_done=True)
+        if qkn:
+            # dqkv's q and k thirds become the gradient of the pre-norm projection, so the QKV bias
+            # gradient is the column sum of THAT (Dense.bwd's own), not the attention backward's
+            K.qk_norm_bwd(dqkv, sv["qk_pre"], self.H, self.Dh, self.q_ln.data, self.k_ln.data,
+                          self.q_ln.grad, self.k_ln.grad, self.QK_LN_EPS)
+        dy0 = self.qkv.bwd(dqkv.view(B * L, 3 * D), sv["y0"].view(B * L, D),
+                           bias_grad_done=not qkn)
         if prev is not None and sv["x"].dtype == torch.float32 and dy0.dtype == torch.bfloat16:
             pblk, psv, pctx = prev
             pkp = psv["kpm"]  # block i-1's MLP-output dropout
@@ -755,12 +784,13 @@ class StackedEncoder1DBlock(Bindable):
     def create(cls, store: ParamStore, name: str, num_blocks: int, D: int, num_heads: int,
                mlp_dim: int, eps: float = 1e-6, dropout_rate: float = 0.1,
                attn_dropout_rate: float = 0.1, fp8: bool = False,
-               fp8_residual: bool = False) -> "StackedEncoder1DBlock":
+               fp8_residual: bool = False, normalize_qk: bool = False) -> "StackedEncoder1DBlock":
         """The stack's blocks declared in ``store`` (the Octo model's path; its posembed_input
         is declared by the model, which adds it inside the fused sequence assembly)."""
         st = cls(num_blocks, None)
         st.blocks = [Encoder1DBlock.create(store, f"{name}/Block_{i}", D, num_heads, mlp_dim, eps,
-                                           dropout_rate, attn_dropout_rate, fp8, fp8_residual)
+                                           dropout_rate, attn_dropout_rate, fp8, fp8_residual,
+                                           normalize_qk)
                      for i in range(num_blocks)]
         st._store, st._name = store, name
         return st

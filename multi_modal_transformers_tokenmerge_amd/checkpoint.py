@@ -288,6 +288,13 @@ def _block_leaves(model):
                     (lambda b, j=j: b.qkv.b.data[j * D:(j + 1) * D].reshape(H, Dh)),
                     (lambda b, a, j=j: b.qkv.b.data[j * D:(j + 1) * D].copy_(
                         torch.from_numpy(a.reshape(-1).copy())))))
+    if getattr(model.cfg, "normalize_qk", False):
+        # flax.linen.SelfAttention(normalize_qk=True): LayerNorm(use_bias=False) named query_ln /
+        # key_ln, one (Dh,) scale each, shared by the heads
+        for n, attr in (("query_ln", "q_ln"), ("key_ln", "k_ln")):
+            out.append((f"SelfAttention_0/{n}/scale", (lambda b, attr=attr: getattr(b, attr).data),
+                        (lambda b, a, attr=attr: getattr(b, attr).data.copy_(
+                            torch.from_numpy(np.ascontiguousarray(a).reshape(-1))))))
     out.append(("SelfAttention_0/out/kernel", lambda b: b.out.w.data.T.reshape(H, Dh, D),
                 lambda b, a: b.out.w.data.copy_(torch.from_numpy(a.reshape(H * Dh, D).T.copy()))))
     out.append(("SelfAttention_0/out/bias", lambda b: b.out.b.data, None))
@@ -405,6 +412,8 @@ class _CpuBlock:
         self.ln1 = stage(blk.ln1, ("scale", "bias"))
         self.qkv = stage(blk.qkv, ("w", "b"))
         self.out = stage(blk.out, ("w", "b"))
+        ln = stage(blk, ("q_ln", "k_ln"))   # None without normalize_qk
+        self.q_ln, self.k_ln = ln.q_ln, ln.k_ln
 
         class _M:
             pass

@@ -16,7 +16,9 @@ which are not available on the GPU box.
   reads (``attention_blocks.stacked_encoder_1d_block.{num_blocks, encoder_1d_block}``,
   ``octo.py:67,80``). New keys: ``token_compression_sequence`` (ToMe),
   ``token_compression_method`` ("tome" | "prune"), ``proportional_attention`` (ToMe's log-size
-  key bias in attention), ``track_merge_source`` (the patch -> merged token map), ``readout_pooling`` ("mean" |
+  key bias in attention), ``track_merge_source`` (the patch -> merged token map),
+  ``...encoder_1d_block.self_attention.normalize_qk`` (Flax's own attribute: QK-norm),
+  ``readout_pooling`` ("mean" |
   "attention": MultiHeadAttentionPooling of the readouts in the diffusion head, with
   ``pooling_heads`` / ``pooling_mlp_dim`` or the head's ``attention_pooling`` node),
   ``action_heads.action_horizon`` (the diffusion head denoises a chunk of that many actions),
@@ -289,6 +291,7 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
     kw["compression"] = str(cfg.get("token_compression_method", "tome"))
     kw["proportional_attention"] = bool(cfg.get("proportional_attention", False))
     kw["track_merge_source"] = bool(cfg.get("track_merge_source", False))
+    kw["normalize_qk"] = bool(sa.get("normalize_qk", False))
     # readout pooling of the diffusion head: the root keys, else the head's attention_pooling node
     # (diffusion.yaml:6-51 of the reference: dot_product_attention.num_heads,
     # mlp_block.dense.features, layer_norm.reduction_axes)

@@ -64,6 +64,12 @@ class OctoConfig:
     # with the step), read back with Octo.merge_source. Needs compression == "tome"; a no-op
     # without token_compression_sequence
     track_merge_source: bool = False
+    # QK-norm (YAML key ...encoder_1d_block.self_attention.normalize_qk, flax.linen.SelfAttention's
+    # own attribute): LayerNorm(use_bias=False) over the head dimension of the projected queries
+    # and keys before the dot product, two (Dh,) scales per block (query_ln / key_ln); everything
+    # that reads the keys (attention, the ToMe metric, the pruning importance) sees them
+    # normalised. Head widths 32 / 64 / 128 / 256
+    normalize_qk: bool = False
     # how the diffusion head turns the readout tokens into its conditioning vector (YAML key
     # readout_pooling): "mean" (the reference's live code path, diffusion.py:102) or "attention"
     # (MultiHeadAttentionPooling, attention.py:122-150, the call the reference left commented out,
@@ -186,6 +192,9 @@ PRESETS = {
     "octo-small-tome16-prop": OctoConfig(name="octo-small-tome16-prop",
                                          token_compression_sequence=TOME16,
                                          proportional_attention=True),
+    # configs[2] with QK-norm (per-head LayerNorm of q and k, the ViT-22B recipe)
+    "octo-small-tome16-qknorm": OctoConfig(name="octo-small-tome16-qknorm",
+                                           token_compression_sequence=TOME16, normalize_qk=True),
     # configs[3]: base, 2 cameras, 2-step history
     "octo-base-2cam": OctoConfig(
         name="octo-base-2cam", token_embedding_dim=768, num_heads=12, mlp_dim=3072,

@@ -120,7 +120,8 @@ class Octo:
         self.stack = StackedEncoder1DBlock.create(store, "StackedEncoder1DBlock_0", cfg.num_blocks,
                                                   D, cfg.num_heads, cfg.mlp_dim, cfg.layer_norm_eps,
                                                   cfg.dropout_rate, cfg.attention_dropout_rate,
-                                                  fp8=cfg.fp8, fp8_residual=cfg.fp8_residual)
+                                                  fp8=cfg.fp8, fp8_residual=cfg.fp8_residual,
+                                                  normalize_qk=cfg.normalize_qk)
         # ---- head
         self.head = DiffusionActionHead.create(store, "diffusion_action_head", D,
                                                cfg.action_space_dim * cfg.action_horizon,
