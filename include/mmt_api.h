@@ -49,7 +49,7 @@ int mmt_version(void);
  * arrays (mmt_tome_merge_wavg_fwd / _bwd, mmt_tome_merge_seqnorm_fwd, mmt_ln_unmerge_dropout_bwd,
  * mmt_gather_rows, mmt_topk_scatter_bwd, mmt_tome_pos_map, mmt_tome_source_step / _groups,
  * mmt_tome_unmerge_fwd / _bwd, mmt_value_tokens_fwd / _bwd, mmt_pc_sample_group,
- * mmt_pc_embed_fwd / _bwd) cannot see those device values at
+ * mmt_pc_embed_fwd / _bwd, mmt_pad_mask_pack) cannot see those device values at
  * launch. Their kernels
  * range-check every index they use; an invalid one is replaced by 0 (so no access leaves its
  * tensor and the context survives) and sets a bit of a library-wide device status word:
@@ -58,6 +58,8 @@ int mmt_version(void);
  *   MMT_FAULT_POS_MAP        pos_map entry not in [0, t - r)
  *   MMT_FAULT_ROW_INDEX      gathered / scattered row not in [0, L); a saved value token not in
  *                            [0, num_bins) (mmt_value_tokens_bwd: the entry is skipped)
+ *   MMT_FAULT_PAD_MASK       a Readout set flagged absent in a set pad mask (mmt_pad_mask_pack:
+ *                            the set is treated as present)
  * mmt_device_status synchronises `stream`, returns MMT_OK if the word is clear, else clears it and
  * returns MMT_ERR_INVALID with the decoded bits in mmt_last_error(). Not graph-capturable (it
  * synchronises); call it after a step, a test or a bench. The reference's jnp gathers cannot fault
@@ -66,7 +68,8 @@ enum {
   MMT_FAULT_TOME_INDEX = 1,
   MMT_FAULT_TOME_PARTITION = 2,
   MMT_FAULT_POS_MAP = 4,
-  MMT_FAULT_ROW_INDEX = 8
+  MMT_FAULT_ROW_INDEX = 8,
+  MMT_FAULT_PAD_MASK = 16
 };
 int mmt_device_status(mmt_stream_t stream);
 
@@ -461,16 +464,18 @@ int mmt_attn_bwd(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H,
                  float keep_prob, const void* o, int64_t o_s_b, int64_t o_s_t, const void* dout,
                  int64_t d_s_b, int64_t d_s_t, const float* lse, float* delta, void* dqkv,
                  int64_t dq_s_b, int64_t dq_s_t, float* bias_grad, mmt_stream_t stream);
-/* The same two with a per-sample, per-key additive logit shared by all heads and queries (ToMe
- * proportional attention, key_bias[b, k] = log size[b, k]: a merged token votes as the patches it
- * stands for):  logits[b,h,q,k] = scale * q.k + key_bias[b,k], then mask, softmax and dropout as
+/* The same two with a per-sample, per-key additive logit shared by all heads and queries. Two
+ * users: ToMe proportional attention, key_bias[b, k] = log size[b, k] (a merged token votes as the
+ * patches it stands for; mmt_tome_size_bias), and the observation pad masks, key_bias[b, k] =
+ * MMT_PAD_MASK_LOGIT on the keys of absent token sets and padded text tokens (mmt_pad_mask_bias);
+ * with both, the two biases add:  logits[b,h,q,k] = scale * q.k + key_bias[b,k], then mask, softmax and dropout as
  * above. key_bias == NULL is mmt_attn_fwd / mmt_attn_bwd (which forward here with NULL).
  * key_bias: fp32, row b at key_bias + b*kb_s_b; kb_s_b a multiple of 4 and >= roundup(L, 64); the
  * base 16-B aligned. Entries [0, L) are used and must be finite; entries [L, roundup(L, 64)) must
  * be readable and are ignored whatever they hold, NaN and Inf included (the kernels load aligned
  * float4s, so L needs no multiple of 4, and mask those keys before the exponent).
  * lse includes the bias and the backward recomputes P with it; no gradient with respect to
- * key_bias is produced (sizes come from the non-differentiable match). Rejected
+ * key_bias is produced (sizes come from the non-differentiable match, masks are data). Rejected
  * (MMT_ERR_INVALID, nothing launched): key_bias with wsum, and key_bias with the T5 `bias`.
  * With key_bias the Dh 64, 32 < L <= 320 backward always takes the two-phase resident kernel. */
 int mmt_attn_fwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L, int H, int Dh,
@@ -493,6 +498,76 @@ int mmt_attn_bwd_keybias(const void* qkv, int64_t s_b, int64_t s_t, int B, int L
  * launch each, the first with zero_rest. */
 int mmt_tome_size_bias(const float* size, int B, int t, int set_start, int L, float* kb,
                        int64_t kb_s_b, int zero_rest, mmt_stream_t stream);
+/* ------------------------------------------------------------------ observation pad masks
+ * Absent token sets (a dataset without a wrist camera, the history of an episode's first steps)
+ * and padded instruction tokens. Upstream Octo's pad_mask_dict / timestep_pad_mask / language
+ * attention mask; the reference has none. A masked token — a token of a set flagged absent for
+ * its sample, or a padded token of the text set — is treated in three ways:
+ *   1. it is never a key with weight: every block adds MMT_PAD_MASK_LOGIT to its key logit through
+ *      the key_bias of mmt_attn_fwd_keybias / mmt_attn_bwd_keybias (mmt_pad_mask_bias);
+ *   2. its content is never read: its row of the assembled sequence x0 is overwritten with
+ *      pos_embedding[row] alone (mmt_pad_mask_rows_fwd, after every tokenizer has written x0);
+ *      and because the image stem's GroupNorm runs over all patches of all cameras of a sample,
+ *      the stem reads a copy of the images with the pixels of absent cameras zeroed
+ *      (mmt_pad_mask_images), so no statistic carries them into a present camera's tokens;
+ *   3. it sends no gradient to a tokenizer: its row of dx0 is zeroed (mmt_pad_mask_rows_bwd) after
+ *      d(pos_embedding) has been taken from the full dx0 and before anything else reads dx0.
+ * MMT_PAD_MASK_LOGIT = -1024: finite, as key_bias requires; exact in fp32, and so is its quotient
+ * by a power-of-two scale (Dh 64 and 256; at Dh 128 the quotient is rounded once). Condition: a
+ * masked key's weight exp(logit + M - rowmax) underflows to exactly 0 in fp32 whenever the spread
+ * of the row's unmasked logits (max - min over the keys the query sees) is below about 900
+ * (1024 - 900 = 124 > 104 = the fp32 denormal underflow point of exp); a larger spread leaves a
+ * weight below 1e-38 times that ratio. A query whose visible keys are ALL masked (the
+ * TaskDescriptionPrefix queries of an absent instruction, the queries of a set that sees only
+ * itself and is absent) gets, by the shift invariance of softmax, the ordinary softmax over those
+ * keys: finite, and read by no present token.
+ * Left as it is: the LayerNorm runs over the sequence axis, so a masked row (its fixed content of
+ * rule 2) still enters its sample's statistics — a sample with an absent set is not a model built
+ * without that set; ToMe matches and merges inside an absent set as usual (sets are matched one by
+ * one, so a set stays wholly present or wholly absent); the frozen T5 is not masked inside.
+ *
+ * Set tables (n_sets, set_start, set_len: HOST arrays, the mmt_attn_fwd convention) must tile
+ * [0, L) with 1 <= n_sets <= MMT_PAD_MASK_MAX_SETS; they are those of the layer the call serves
+ * (the starts follow the shrinking sequence under ToMe). words: uint32 [B] from mmt_pad_mask_pack,
+ * bit s set = set s present (NULL: every set present). text_mask: bytes (B, T) contiguous,
+ * nonzero = real token, for the tokens of set text_set, T == set_len[text_set] (NULL: none); at
+ * least one of the two is given. Checked before any launch (MMT_ERR_INVALID): null pointers,
+ * n_sets, the tiling, T, text_set, and per entry point the alignment and stride rules below. */
+#define MMT_PAD_MASK_LOGIT (-1024.0f)
+#define MMT_PAD_MASK_MAX_SETS 16
+/* words[b] = the present-bits of set_mask (bytes (B, n_sets) contiguous, nonzero = present).
+ * readout_bits: the bit mask of the Readout sets, which cannot be absent (they carry the
+ * prediction): one flagged absent is reported through the device status word
+ * (MMT_FAULT_PAD_MASK, mmt_device_status) and treated as present, so its bit is set. */
+int mmt_pad_mask_pack(const uint8_t* set_mask, int B, int n_sets, uint32_t readout_bits,
+                      uint32_t* words, mmt_stream_t stream);
+/* dst = src (B, I, image_bytes: the camera images, any pixel type) with the image_bytes of
+ * image (b, i) zeroed where set image_set[i] (HOST array of I set indices in [0, n_sets)) is
+ * absent in words[b]. src is not changed; src != dst, both 16-B aligned, image_bytes a multiple of
+ * 16 (16-B vector moves), I <= 16, B * I <= 65535. A zero byte is pixel 0 (uint8) or 0.0 (fp32). */
+int mmt_pad_mask_images(const uint32_t* words, const int32_t* image_set, int n_sets, int B, int I,
+                        int64_t image_bytes, const void* src, void* dst, mmt_stream_t stream);
+/* The key_bias rows of one layer: kb fp32, row b at kb + b*kb_s_b, 16-B aligned, kb_s_b a multiple
+ * of 4 and >= roundup(L, 64). accumulate == 0: kb[b, l] = MMT_PAD_MASK_LOGIT (masked) or 0 over
+ * [0, L) and 0 over the padding [L, roundup(L, 64)). accumulate != 0: kb[b, l] +=
+ * MMT_PAD_MASK_LOGIT on the masked entries and nothing else is touched — launched after
+ * mmt_tome_size_bias has written the rows (proportional attention: the two biases add). */
+int mmt_pad_mask_bias(const uint32_t* words, int B, int L, int n_sets, const int32_t* set_start,
+                      const int32_t* set_len, const uint8_t* text_mask, int text_set, int T,
+                      float* kb, int64_t kb_s_b, int accumulate, mmt_stream_t stream);
+/* x0[b, l, :] = pe[l, :] on the masked rows of the fp32 (B, L, D) sequence (row (b, l) at
+ * x0 + b*xs_b + l*xs_t; pe fp32 (L, D) contiguous); rows of present tokens are neither read nor
+ * written. D % 4 == 0, x0 and pe 16-B aligned, xs_t >= D, xs_b >= (L-1)*xs_t + D, both strides
+ * multiples of 4 (rows move as 16-B vectors). The set table is layer 0's. */
+int mmt_pad_mask_rows_fwd(const uint32_t* words, int B, int L, int D, int n_sets,
+                          const int32_t* set_start, const int32_t* set_len,
+                          const uint8_t* text_mask, int text_set, int T, const float* pe,
+                          float* x0, int64_t xs_b, int64_t xs_t, mmt_stream_t stream);
+/* dx0[b, l, :] = 0 on the same rows, in place; the same rules. */
+int mmt_pad_mask_rows_bwd(const uint32_t* words, int B, int L, int D, int n_sets,
+                          const int32_t* set_start, const int32_t* set_len,
+                          const uint8_t* text_mask, int text_set, int T, float* dx0, int64_t xs_b,
+                          int64_t xs_t, mmt_stream_t stream);
 /* Keep mask of a dropout stream (flax Dropout keep-mask, broadcast over batch and heads for
  * attention): keep(r, c) iff keep_elem(key(rng, layer, site), r*cols + c), i.e. the 16-bit half
  * (idx & 1) of mix32(key ^ (idx >> 1)) is below floor(keep_prob * 65536).

@@ -68,6 +68,11 @@ SIGNATURES: dict[str, list] = {
     "mmt_attn_bwd_keybias": [P, L, L, I, I, I, I, F, I, P, P, P, P, P, F, P, L, L, P, L, L, P, P, P,
                              L, L, P, P, L, P],
     "mmt_tome_size_bias": [P, I, I, I, I, P, L, I, P],
+    "mmt_pad_mask_pack": [P, I, I, U32, P, P],
+    "mmt_pad_mask_images": [P, P, I, I, I, L, P, P, P],
+    "mmt_pad_mask_bias": [P, I, I, I, P, P, P, I, I, P, L, I, P],
+    "mmt_pad_mask_rows_fwd": [P, I, I, I, I, P, P, P, I, I, P, P, L, L, P],
+    "mmt_pad_mask_rows_bwd": [P, I, I, I, I, P, P, P, I, I, P, L, L, P],
     "mmt_tome_pos_map": [P, P, P, I, I, I, I, P, P],
     "mmt_tome_source_step": [P, I, I, I, P, I, I, P],
     "mmt_tome_source_groups": [P, I, I, I, P, P, P],
@@ -344,6 +349,9 @@ def diffusion_loss_last_route() -> int:
     return call("mmt_diffusion_loss_last_route")
 
 
+# observation pad masks (include/mmt_api.h): the key logit of a masked token, the set limit, the
+# device status bit of a Readout set flagged absent
+PAD_MASK_LOGIT, PAD_MASK_MAX_SETS, FAULT_PAD_MASK = -1024.0, 16, 16
 VALUE_UNIFORM, VALUE_MU_LAW = 0, 1   # MMT_VALUE_* (mmt_value_tokens_fwd encoding)
 VALUE_MIN_BINS, VALUE_MAX_BINS = 2, 4096
 # MMT_PC_* limits of the point-cloud tokenizer (mmt_pc_sample_group, mmt_pc_embed_fwd / _bwd)

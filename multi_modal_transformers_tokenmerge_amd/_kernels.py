@@ -666,6 +666,135 @@ def tome_size_bias(B: int, L: int, sets, out: torch.Tensor | None = None) -> tor
     return out
 
 
+# ----------------------------------------------------------------- observation pad masks
+PAD_MASK_LOGIT = _C.PAD_MASK_LOGIT   # MMT_PAD_MASK_LOGIT: the key logit of a masked token
+
+
+def _pad_sets(sets):
+    """(n, starts, lens) of a layer's set table — a SetTable, a LayerSets or any (starts, lens)
+    pair — as the host int32 arrays the C ABI takes."""
+    if isinstance(sets, SetTable):
+        return sets.n, sets.starts, sets.lens
+    starts, lens = (sets.starts, sets.lens) if hasattr(sets, "starts") else sets
+    n = len(starts)
+    if len(lens) != n:
+        raise ValueError("set table: starts and lens differ in length")
+    return n, (_C.ctypes.c_int32 * max(n, 1))(*starts), (_C.ctypes.c_int32 * max(n, 1))(*lens)
+
+
+def _pad_mask_args(B: int, words, text_mask, text_set: int):
+    """Host checks of the (words, text mask) pair every pad-mask kernel takes; returns T."""
+    _dev(words, text_mask)
+    if words is None and text_mask is None:
+        raise ValueError("pad mask: neither the packed set mask nor a text mask")
+    if words is not None and (words.dtype != torch.int32 or tuple(words.shape) != (B,)
+                              or not words.is_contiguous()):
+        raise ValueError(f"words must be contiguous int32 ({B},) (pad_mask_pack builds it)")
+    if text_mask is None:
+        return 0
+    if (text_mask.dtype != torch.bool or text_mask.dim() != 2 or text_mask.shape[0] != B
+            or not text_mask.is_contiguous()):
+        raise ValueError(f"text_mask must be a contiguous bool (B={B}, T) tensor")
+    if text_set < 0:
+        raise ValueError("text_mask needs the index of its token set (text_set)")
+    return text_mask.shape[1]
+
+
+def pad_mask_pack(set_mask: torch.Tensor, readout_bits: int = 0,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """set_mask bool (B, n_sets), True = the set is present -> int32 (B,) words of present-bits
+    (mmt_pad_mask_pack). readout_bits: the bit mask of the Readout sets; one flagged absent is
+    reported by device_status() (MMT_FAULT_PAD_MASK) and treated as present."""
+    _dev(set_mask, out)
+    if set_mask.dim() != 2 or set_mask.dtype != torch.bool or not set_mask.is_contiguous():
+        raise ValueError("set_mask must be a contiguous bool (B, n_sets) tensor")
+    B, n = set_mask.shape
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int32, device=set_mask.device)
+    elif tuple(out.shape) != (B,) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous int32 ({B},)")
+    _C.call("mmt_pad_mask_pack", ptr(set_mask), B, n, readout_bits, ptr(out), _C.stream_ptr())
+    return out
+
+
+def pad_mask_images(images: torch.Tensor, words: torch.Tensor, image_sets, n_sets: int,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """A copy of the camera images (B, I, H, W, C), uint8 or fp32, contiguous, with the pixels of
+    image (b, i) zeroed where set image_sets[i] is absent in words[b] (mmt_pad_mask_images): what
+    the image stem reads under a set pad mask, since its GroupNorm runs over all patches of all
+    cameras of a sample. `images` itself is not changed."""
+    _dev(images, words, out)
+    if images.dim() < 3 or not images.is_contiguous():
+        raise ValueError("images must be a contiguous (B, I, ...) tensor")
+    B, I = images.shape[:2]
+    image_sets = list(image_sets)
+    if len(image_sets) != I:
+        raise ValueError(f"image_sets names {len(image_sets)} sets for {I} images per sample")
+    if words.dtype != torch.int32 or tuple(words.shape) != (B,) or not words.is_contiguous():
+        raise ValueError(f"words must be contiguous int32 ({B},) (pad_mask_pack builds it)")
+    if out is None:
+        out = torch.empty_like(images)
+    elif out.shape != images.shape or out.dtype != images.dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor of the images' shape and dtype")
+    nbytes = images[0, 0].numel() * images.element_size()
+    _C.call("mmt_pad_mask_images", ptr(words), (_C.ctypes.c_int32 * max(I, 1))(*image_sets), n_sets,
+            B, I, nbytes, ptr(images), ptr(out), _C.stream_ptr())
+    return out
+
+
+def pad_mask_bias(B: int, L: int, sets, words: torch.Tensor | None,
+                  text_mask: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                  accumulate: bool = False, text_set: int = 0) -> torch.Tensor:
+    """The pad masks as the key bias of one layer (mmt_pad_mask_bias): fp32 (B, attn_lp(L)) with
+    PAD_MASK_LOGIT on the keys of absent sets (words: pad_mask_pack's, None = all present) and on
+    the padded tokens of set text_set (text_mask bool (B, T), True = real), 0 elsewhere and on the
+    padding. sets: the layer's set table. accumulate (out given): PAD_MASK_LOGIT is added to the
+    masked entries of the rows tome_size_bias wrote and nothing else is touched. out may be a
+    (B, attn_lp(L)) view of wider rows."""
+    n, starts, lens = _pad_sets(sets)
+    T = _pad_mask_args(B, words, text_mask, text_set)
+    _dev(out)
+    if out is None:
+        if accumulate:
+            raise ValueError("pad_mask_bias(accumulate=True) needs the rows to add to (out=)")
+        dev = (words if words is not None else text_mask).device
+        out = torch.empty((B, attn_lp(L)), dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (B, attn_lp(L)) or out.dtype != torch.float32 or out.stride(1) != 1):
+        raise ValueError(f"out must be fp32 (B, attn_lp(L)) = {(B, attn_lp(L))}, unit inner stride")
+    _C.call("mmt_pad_mask_bias", ptr(words), B, L, n, starts, lens, ptr(text_mask), text_set, T,
+            ptr(out), out.stride(0), int(bool(accumulate)), _C.stream_ptr())
+    return out
+
+
+def _pad_rows(name: str, x: torch.Tensor, sets, words, text_mask, text_set, pe):
+    _dev(x, pe)
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError("the sequence must be fp32 (B, L, D) with unit stride along D")
+    B, L, D = x.shape
+    n, starts, lens = _pad_sets(sets)
+    T = _pad_mask_args(B, words, text_mask, text_set)
+    args = (ptr(words), B, L, D, n, starts, lens, ptr(text_mask), text_set, T)
+    if pe is not None:
+        if tuple(pe.shape) != (L, D) or pe.dtype != torch.float32 or not pe.is_contiguous():
+            raise ValueError(f"pe must be contiguous fp32 (L, D) = {(L, D)}")
+        args += (ptr(pe),)
+    _C.call(name, *args, ptr(x), x.stride(0), x.stride(1), _C.stream_ptr())
+    return x
+
+
+def pad_mask_rows_fwd(x0: torch.Tensor, pe: torch.Tensor, sets, words,
+                      text_mask: torch.Tensor | None = None, text_set: int = 0) -> torch.Tensor:
+    """x0[b, l] = pe[l] on the masked rows of the assembled fp32 (B, L, D) sequence, in place
+    (mmt_pad_mask_rows_fwd); the other rows are not touched. sets: layer 0's table."""
+    return _pad_rows("mmt_pad_mask_rows_fwd", x0, sets, words, text_mask, text_set, pe)
+
+
+def pad_mask_rows_bwd(dx0: torch.Tensor, sets, words, text_mask: torch.Tensor | None = None,
+                      text_set: int = 0) -> torch.Tensor:
+    """dx0[b, l] = 0 on the masked rows, in place (mmt_pad_mask_rows_bwd)."""
+    return _pad_rows("mmt_pad_mask_rows_bwd", dx0, sets, words, text_mask, text_set, None)
+
+
 # ------------------------------------------------------------------------ seq LayerNorm etc.
 def _seq_out(out, shape, dtype, device, what: str):
     """`out` or a fresh (B, L, D) tensor; a given one may be a strided view (unit stride along D)."""

@@ -64,6 +64,16 @@ class LayerCtx:
     #                                none itself (else: the block's merged set)
     track_source: bool = False     # merge source: compose every merge's pos_map into the set's
     #                                patch -> merged token map (OctoConfig.track_merge_source)
+    # observation pad masks (include/mmt_api.h): the packed present-bits of the token sets
+    # (K.pad_mask_pack, int32 (B,)) and the text set's token mask (bool (B, T), True = real) with
+    # the index of that set; both None: no mask, not one launch added
+    pad_words: Optional[torch.Tensor] = None
+    text_mask: Optional[torch.Tensor] = None
+    text_set: int = -1
+
+    @property
+    def pad_masked(self) -> bool:
+        return self.pad_words is not None or self.text_mask is not None
 
     def tome_sets(self):
         """The merged sets as ((set index, r), ...)."""
@@ -465,18 +475,36 @@ class Encoder1DBlock(Bindable):
         self.scale = self.Dh ** -0.5
 
     def __call__(self, inputs: torch.Tensor, mask=None, train=None, *, rng=None, layer: int = 0,
-                 sample_offset: int = 0):
+                 sample_offset: int = 0, set_pad_mask=None, text_pad_mask=None, text_set: int = 0,
+                 readout_bits: int = 0):
         """inputs (B, L, D) -> (x, None), x fp32 (B, L, D). ``mask``: the dense reference mask
         (or a token-set table); ``rng``: the 'dropout' collection, a (seed, step) int32 device
         tensor (needed when train and a rate > 0); ``layer`` / ``sample_offset`` key the dropout
-        streams like the Octo path (block index, global index of the first sample)."""
+        streams like the Octo path (block index, global index of the first sample).
+        ``set_pad_mask`` bool (B, number of sets of ``mask``), ``text_pad_mask`` bool (B, tokens
+        of set ``text_set``), True = real: the observation pad masks as this block's key bias
+        (masked keys get no attention weight; the rows of ``inputs`` are the caller's).
+        ``readout_bits``: the bit mask of the sets that cannot be absent (the Readout sets; a
+        dense mask does not say which they are): one of them flagged absent is reported by
+        K.device_status() (MMT_FAULT_PAD_MASK) and treated as present. With the default 0 every
+        flagged set is masked and nothing is reported."""
         train = bool(merge_param("train", self.train, train))
         mask = merge_param("mask", self.mask, mask)
         if inputs.dim() != 3:
             raise ValueError(f"inputs must be (batch, length, features), got {tuple(inputs.shape)}")
+        table = set_table_of(mask, inputs.shape[1])
+        B = inputs.shape[0]
+        check_pad_masks(set_pad_mask, text_pad_mask, B, table.n,
+                        table.lens[text_set] if 0 <= text_set < table.n else -1)
+        if readout_bits < 0 or readout_bits >> table.n:
+            raise ValueError(f"readout_bits {readout_bits:#x} names a set past the {table.n} sets "
+                             "of the set_pad_mask")
         self._ensure(inputs.device, int(inputs.shape[-1]))
-        ctx = LayerCtx(layer=layer, sets=None, table=set_table_of(mask, inputs.shape[1]),
-                       train=train, rng=rng, sample_offset=sample_offset)
+        ctx = LayerCtx(layer=layer, sets=None, table=table,
+                       train=train, rng=rng, sample_offset=sample_offset,
+                       pad_words=(None if set_pad_mask is None
+                                  else K.pad_mask_pack(set_pad_mask, readout_bits)),
+                       text_mask=text_pad_mask, text_set=text_set)
         if train and (self.rate > 0 or self.attn_rate > 0 or self.mlp.rate > 0) and rng is None:
             raise ValueError("Encoder1DBlock(train=True) needs the dropout rng (rng=)")
         x = inputs.float().contiguous()
@@ -556,6 +584,14 @@ class Encoder1DBlock(Bindable):
             sized = ctx.sized_sets(size)
             if sized:
                 kbias = K.tome_size_bias(B, L, sized)
+        if ctx.pad_masked:
+            # pad masks: MMT_PAD_MASK_LOGIT on the keys of absent sets and padded text tokens, by
+            # this layer's set table; added to the proportional-attention rows when there are any
+            if wsum is not None:
+                raise ValueError("pad masks cannot be combined with top-k pruning (key_bias "
+                                 "cannot be combined with wsum)")
+            kbias = K.pad_mask_bias(B, L, ctx.table, ctx.pad_words, ctx.text_mask, out=kbias,
+                                    accumulate=kbias is not None, text_set=ctx.text_set)
         o, lse = K.attn_fwd(qkv, H, self.scale, ctx.table, bits, kpa, wsum=wsum, key_bias=kbias)
         prune = None
         o_in, x_res, Lo = o, x, L
@@ -704,6 +740,26 @@ class Encoder1DBlock(Bindable):
                 pctx.sample_offset * L, colsum=pblk.mlp.dense_out.b.grad)
             return dx, dzp.view(B * L, D)
         return self.ln0.bwd(dy0.view(B, L, D), sv["x"], sv["mu0"], sv["rs0"], addend=dx1), None
+
+
+def check_pad_masks(set_pad_mask, text_pad_mask, B: int, n_sets: int, T: int, device=None):
+    """The observation pad masks checked on the host, before any launch. ValueError: not a bool
+    tensor, set_pad_mask not (B, n_sets), text_pad_mask not (B, T) (T < 0: there is no text set to
+    speak of), or a tensor off ``device`` (given: the model's device type)."""
+    for name, m, shape in (("set_pad_mask", set_pad_mask, (B, n_sets)),
+                           ("text_pad_mask", text_pad_mask, (B, T))):
+        if m is None:
+            continue
+        if not torch.is_tensor(m) or m.dtype != torch.bool:
+            raise ValueError(f"{name} must be a bool tensor (True = real)")
+        if name == "text_pad_mask" and T < 0:
+            raise ValueError("text_pad_mask given, but the sequence has no text set")
+        if tuple(m.shape) != shape:
+            raise ValueError(f"{name} {tuple(m.shape)}: expected {shape}")
+        if device is not None and m.device.type != torch.device(device).type:
+            raise ValueError(f"{name} must live on the model's device ({torch.device(device).type})")
+        if not m.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
 
 
 def set_table_of(mask, L: int) -> K.SetTable:

@@ -58,12 +58,14 @@ extern "C" int mmt_device_status(mmt_stream_t stream) {
     mmt::set_error("mmt_device_status: clear failed: %s", hipGetErrorString(hipGetLastError()));
     return MMT_ERR_HIP;
   }
-  char what[256] = "";
+  char what[384] = "";
   static const struct { unsigned int bit; const char* name; } names[] = {
       {MMT_FAULT_TOME_INDEX, "ToMe merge: unm/src/dst index out of range"},
       {MMT_FAULT_TOME_PARTITION, "ToMe merge: unm and src do not partition the a half (index repeated)"},
       {MMT_FAULT_POS_MAP, "ToMe unmerge: pos_map entry out of range"},
-      {MMT_FAULT_ROW_INDEX, "row gather / scatter: row index out of range"}};
+      {MMT_FAULT_ROW_INDEX, "row gather / scatter: row index out of range"},
+      {MMT_FAULT_PAD_MASK, "MMT_FAULT_PAD_MASK: a Readout set flagged absent in set_pad_mask "
+                           "(treated as present)"}};
   for (const auto& nm : names)
     if (v & nm.bit) {
       if (what[0]) strncat(what, "; ", sizeof what - strlen(what) - 1);

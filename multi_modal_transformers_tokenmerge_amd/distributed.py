@@ -101,10 +101,12 @@ class DDPStep:
     # values: the numbers behind the model's Value sets (Octo.generate_readouts), a static device
     # buffer read by every replay like img and act; required with Value sets, refused without.
     # point_clouds: the clouds behind its PointCloud sets, a static device buffer likewise.
+    # set_pad_mask, text_pad_mask: the observation pad masks (Octo.generate_readouts), static bool
+    # device buffers likewise: a replay after the loader rewrote them gives the other masks' step.
 
     def __init__(self, model, state, txt, img, act, reducer: GradAllReducer | None = None,
                  stages="auto", use_graph: bool = True, txt_next=None, values=None,
-                 point_clouds=None):
+                 point_clouds=None, set_pad_mask=None, text_pad_mask=None):
         self.model, self.state = model, state
         self.txt, self.img, self.act = txt, img, act
         if values is not None or model.n_values:    # ValueError now, not inside a capture
@@ -116,6 +118,13 @@ class DDPStep:
         self.point_clouds = point_clouds
         if point_clouds is not None:
             self._vkw["point_clouds"] = point_clouds
+        if set_pad_mask is not None or text_pad_mask is not None:
+            model._check_pad_masks(set_pad_mask, text_pad_mask, img.shape[0], img)
+        self.set_pad_mask, self.text_pad_mask = set_pad_mask, text_pad_mask
+        if set_pad_mask is not None:
+            self._vkw["set_pad_mask"] = set_pad_mask
+        if text_pad_mask is not None:
+            self._vkw["text_pad_mask"] = text_pad_mask
         self.t5_pf = (txt_next is not None and txt is not None
                       and getattr(model, "t5", None) is not None)
         self.txt_next = txt_next

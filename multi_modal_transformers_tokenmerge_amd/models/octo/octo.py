@@ -41,7 +41,7 @@ from ...action_heads.categorical import CategoricalActionHead
 from ...action_heads.continuous import ContinuousActionHead, chunk_flat
 from ...action_heads.diffusion import DiffusionActionHead
 from ...attention_blocks.attention import (LayerCtx, MultiHeadAttentionPooling,
-                                           StackedEncoder1DBlock)
+                                           StackedEncoder1DBlock, check_pad_masks)
 from ...layers import Dense, wgrad_overlap
 from ...params import GROUP_CHUNK, ParamStore, he_normal, normal
 from ...schedules import (Constant, ConstantEmaDecay, EmaDecay, Schedule, WarmupCosine,
@@ -74,6 +74,10 @@ class Octo:
         self.D = D
         self.seq = TokenSequence(cfg.input_sequence, cfg.token_compression_sequence)
         sets0 = self.seq.token_sequence
+        # observation pad masks: set_pad_mask's second dimension, the Readout sets (never
+        # absent), the set text_pad_mask speaks of (-1: none)
+        self.n_sets, self.readout_set_bits, self.text_set = self.seq.pad_mask_layout()
+        self.image_sets = [i for i, ts in enumerate(sets0) if isinstance(ts, Image)]
         self.L0 = sum(ts.num_tokens for ts in sets0)
         self.n_images = sum(isinstance(ts, Image) for ts in sets0)
         self.n_text = sum(ts.num_tokens for ts in sets0 if isinstance(ts, Text))
@@ -273,14 +277,17 @@ class Octo:
             self.readout_group = torch.from_numpy(grp).to(self.device)
             self.readout_group_counts = torch.full((G,), per, dtype=torch.int32, device=self.device)
 
-    def layer_ctxs(self, train: bool, rng, sample_offset: int) -> List[LayerCtx]:
+    def layer_ctxs(self, train: bool, rng, sample_offset: int, pad=None) -> List[LayerCtx]:
+        """pad: (packed set words, text token mask) of the observation pad masks, or None."""
         prop = bool(self.cfg.proportional_attention)
         track = bool(self.cfg.track_merge_source)
+        words, text_mask = pad if pad is not None else (None, None)
         ctxs, carried = [], -1  # carried: the set whose sizes the last single-set merge handed on
         for i, (s, t, ts, r, pr, plan) in enumerate(self.layer_sets):
             ctxs.append(LayerCtx(layer=i, sets=s, table=t, tome_set=ts, r=r, prune=pr, train=train,
                                  rng=rng, sample_offset=sample_offset, tome_plan=plan,
-                                 prop_attn=prop, size_set=carried, track_source=track))
+                                 prop_attn=prop, size_set=carried, track_source=track,
+                                 pad_words=words, text_mask=text_mask, text_set=self.text_set))
             if len(plan) == 1:
                 carried = plan[0][0]
         return ctxs
@@ -335,9 +342,41 @@ class Octo:
             raise ValueError(f"fps_start must be an int32 {shape[:2]} tensor on the model's device")
         return point_clouds
 
+    def _check_pad_masks(self, set_pad_mask, text_pad_mask, B: int, images=None) -> bool:
+        """The observation pad masks checked before any launch; returns whether one is given.
+        ValueError: not a bool tensor on the model's device, set_pad_mask not (B, the set count
+        of input_sequence after the repeat expansion), text_pad_mask not (B, the tokens of the
+        first text set), text_pad_mask without a text set or with a compressed one, either
+        mask with compression == "prune" (key_bias cannot be combined with wsum), and, with
+        set_pad_mask and `images` (the (B, I, H, W, C) batch whose absent cameras
+        mmt_pad_mask_images zeroes in a copy), more than 65,535 images or an image whose bytes
+        are no multiple of 16."""
+        if set_pad_mask is None and text_pad_mask is None:
+            return False
+        if self.cfg.compression == "prune":
+            raise ValueError('pad masks cannot be combined with compression == "prune": the '
+                             "attention's key_bias cannot be combined with wsum")
+        T = -1
+        if self.text_set >= 0:
+            ts = self.seq.token_sequence[self.text_set]
+            T = ts.num_tokens
+            if text_pad_mask is not None and ts.tokens_compressed_per_layer:
+                raise ValueError("text_pad_mask: the text set is compressed (per-token masks of "
+                                 "compressed sets are not supported)")
+        check_pad_masks(set_pad_mask, text_pad_mask, B, self.n_sets, T, self.device)
+        if set_pad_mask is not None and images is not None and self.image_sets:
+            I = len(self.image_sets)
+            nbytes = images[0, 0].numel() * images.element_size()
+            if B * I > 65535 or nbytes % 16:
+                raise ValueError(f"set_pad_mask: the images of absent cameras are zeroed in a copy "
+                                 f"moved as 16-B vectors, one grid row per image: B * I = {B * I} "
+                                 f"must be <= 65535 and the bytes of an image ({nbytes}) a "
+                                 "multiple of 16")
+        return True
+
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
                           positions=None, tome=None, t5_out=None, values=None, point_clouds=None,
-                          fps_start=None):
+                          fps_start=None, set_pad_mask=None, text_pad_mask=None):
         """Reference :91-126. Returns the final sequence (B, L_final, D) and the saved state.
         t5_out: the frozen T5 encoder's output for text_tokens, computed ahead (DDPStep's
         cross-step T5 pipeline); None runs the encoder here. values: the numbers behind the
@@ -346,11 +385,20 @@ class Octo:
         input_sequence, refused without. point_clouds: the clouds behind the PointCloud sets,
         fp32 (B, n_sets, P, C) (tokenizers/pointclouds/point_cloud_tokenizer.py), required and
         refused likewise; fps_start (tests): int32 (B, n_sets), the first sampled point of every
-        cloud instead of the step's own (train: drawn, eval: point 0)."""
+        cloud instead of the step's own (train: drawn, eval: point 0).
+        set_pad_mask, text_pad_mask (the observation pad masks, both optional, bool, True = real):
+        set_pad_mask (B, n_sets) flags the token sets of input_sequence, in sequence order after
+        the repeat expansion, that a sample has (a dataset without a wrist camera; a history step
+        is absent when all its sets are); text_pad_mask (B, T) flags the real tokens of the first
+        text set (an instruction's attention_mask). A masked token gets no attention weight as a
+        key in any block, its row of the assembled sequence holds pos_embedding alone whatever
+        the caller passed for it, and no gradient reaches a tokenizer through it (DESIGN.md,
+        "Observation pad masks"). Readout sets cannot be absent (reported by K.device_status())."""
         B = images.shape[0]
         D = self.D
         values = self._check_values(values, B)
         point_clouds = self._check_point_clouds(point_clouds, B, fps_start)
+        padded = self._check_pad_masks(set_pad_mask, text_pad_mask, B, images)
         st: Dict = dict(B=B, train=train, rng=rng, sample_offset=sample_offset)
         txt, T = None, max(self.n_text, 1)
         if self.has_text:
@@ -362,6 +410,17 @@ class Octo:
                 txt = self.text_proj.fwd(t5_out.view(B * self.n_text, -1)).view(B, self.n_text, D)
             else:
                 txt = t5_out
+        pad = None
+        if padded:
+            words = (None if set_pad_mask is None
+                     else K.pad_mask_pack(set_pad_mask, self.readout_set_bits))
+            pad = st["pad"] = (words, text_pad_mask)
+            if words is not None and self.image_sets:
+                # the stem's GroupNorm runs over all patches of all cameras of a sample: it reads
+                # a copy of the images with the absent cameras' pixels zeroed, so they reach no
+                # present camera's tokens through its statistics
+                images = K.pad_mask_images(images.contiguous(), words, self.image_sets,
+                                           self.n_sets)
         with phase("fwd/stem"):
             img_tok, (rt, ct), isv = self.image_tokenizer.forward(images, train, rng, sample_offset,
                                                                   positions)
@@ -379,7 +438,11 @@ class Octo:
             st["pc_sv"] = self.point_cloud_tokenizer.forward(
                 point_clouds, self.pc_tokens, self.pc_rows, self.pos_embed.data, x0, train, rng,
                 sample_offset, fps_start)
-        ctxs = self.layer_ctxs(train, rng, sample_offset)
+        if padded:
+            # after every tokenizer has written x0: the masked rows hold pos_embedding alone
+            K.pad_mask_rows_fwd(x0, self.pos_embed.data, self.layer_sets[0][1], words,
+                                text_pad_mask, self.text_set)
+        ctxs = self.layer_ctxs(train, rng, sample_offset, pad)
         if tome is not None:  # injected ToMe index triples (tests: the golden step fixtures)
             for c, idx in zip(ctxs, tome):
                 c.tome_forced = idx
@@ -413,7 +476,8 @@ class Octo:
 
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
                                        sample_offset=0, inject: Optional[dict] = None, t5_out=None,
-                                       action_pad_mask=None, values=None, point_clouds=None):
+                                       action_pad_mask=None, values=None, point_clouds=None,
+                                       set_pad_mask=None, text_pad_mask=None):
         """Reference :139-145. Returns (loss (1,) fp32 device tensor, saved state). inject (tests):
         positions (rt, ct), t, eps, tome (per block an (unm, src, dst) triple of int32 device
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
@@ -424,7 +488,7 @@ class Octo:
         OctoConfig.n_diffusion_samples = K > 1 (K independent (t, eps) draws per sample; inject
         t (K, B) / eps (K, B, h a)), the head runs its fused multi-draw loss on the pooled readout
         (DiffusionActionHead.loss_forward_multi). values, point_clouds: generate_readouts'
-        (inject fps_start: its fps_start)."""
+        (inject fps_start: its fps_start), and so are set_pad_mask and text_pad_mask."""
         inject = inject or {}
         actions = self._chunk_flat(actions)
         multi = self.cfg.n_diffusion_samples > 1 or action_pad_mask is not None
@@ -437,6 +501,7 @@ class Octo:
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         inject.get("positions"), inject.get("tome"), t5_out,
                                         values=values, point_clouds=point_clouds,
+                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
                                         fps_start=inject.get("fps_start"))
         B = xL.shape[0]
         if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
@@ -473,16 +538,19 @@ class Octo:
 
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
                                        sample_offset=0, train=True, values=None,
-                                       point_clouds=None):
+                                       point_clouds=None,
+                                       set_pad_mask=None, text_pad_mask=None):
         """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
         pooling) -> OctoDenoise (diffusion.py:88-107)."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values, point_clouds=point_clouds)
+                                       values=values, point_clouds=point_clouds,
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         return self.head.predict_denoise_term_mean(self._readout_pooled(xL), time, noisy_actions)
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
                                  positions=None, sampler=None, values=None, point_clouds=None,
+                                 set_pad_mask=None, text_pad_mask=None,
                                  fps_start=None):
         """Reference :147-154: readouts (the reference's backbone always runs with
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
@@ -492,6 +560,7 @@ class Octo:
         and the returned noise stay flat, (B, h a))."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions,
                                        values=values, point_clouds=point_clouds,
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
                                        fps_start=fps_start)
         if self.pooling is not None:
             e = self._readout_pooled(xL)
@@ -542,11 +611,13 @@ class Octo:
         return head
 
     def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                                  values=None, point_clouds=None):
+                                  values=None, point_clouds=None,
+                                  set_pad_mask=None, text_pad_mask=None):
         """Reference :158-165 -> (B, pred_horizon, A) fp32 ((B, 1, A) as the reference)."""
         h = self._need(self.continuous_head, "continuous")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values, point_clouds=point_clouds)
+                                       values=values, point_clouds=point_clouds,
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         return h.forward(self._readout_mean(xL))
 
     @staticmethod
@@ -555,7 +626,8 @@ class Octo:
             raise ValueError("action_pad_mask must be a bool tensor")
 
     def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None, values=None, point_clouds=None):
+                        action_pad_mask=None, values=None, point_clouds=None,
+                        set_pad_mask=None, text_pad_mask=None):
         """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved).
         actions (B, pred_horizon, A) or flat; OctoConfig.continuous_loss picks the squared error
         or L1. action_pad_mask: bool, the actions' shape, True where a component is real: padded
@@ -564,41 +636,48 @@ class Octo:
         h = self._need(self.continuous_head, "continuous")
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                        values=values, point_clouds=point_clouds)
+                                        values=values, point_clouds=point_clouds,
+                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
     def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True,
-                              values=None, point_clouds=None):
+                              values=None, point_clouds=None,
+                              set_pad_mask=None, text_pad_mask=None):
         """Reference :178-185 -> (B, A, num_bins) fp32, (B, pred_horizon, A, num_bins) with a
         pred_horizon > 1."""
         h = self._need(self.categorical_head, "categorical")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                       values=values, point_clouds=point_clouds)
+                                       values=values, point_clouds=point_clouds,
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         return h.forward(self._readout_group_means(xL))
 
     def predict_categorical_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
                                    mode="argmax", temperature=1.0, values=None,
-                                   point_clouds=None):
+                                   point_clouds=None,
+                                   set_pad_mask=None, text_pad_mask=None):
         """The categorical head rolled out: logits (predict_action_logits) decoded to actions
         (B, pred_horizon, A) fp32 through bin_values, by argmax or (mode "sample") one draw per
         component from softmax(logits / temperature) keyed by rng and sample_offset
         (CategoricalActionHead.decode)."""
         h = self._need(self.categorical_head, "categorical")
         logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train,
-                                            values=values, point_clouds=point_clouds)
+                                            values=values, point_clouds=point_clouds,
+                                            set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         return h.decode(logits, rng, sample_offset, mode, temperature)[0]
 
     def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
-                        action_pad_mask=None, values=None, point_clouds=None):
+                        action_pad_mask=None, values=None, point_clouds=None,
+                        set_pad_mask=None, text_pad_mask=None):
         """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved).
         actions (B, pred_horizon, A) or flat. action_pad_mask: compute_l2_loss's; the loss is the
         mean of the cross entropy over the real components."""
         h = self._need(self.categorical_head, "categorical")
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
-                                        values=values, point_clouds=point_clouds)
+                                        values=values, point_clouds=point_clouds,
+                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
         loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
@@ -830,6 +909,13 @@ class Octo:
         dimg = torch.empty((B, NI, D), dtype=torch.bfloat16, device=dx0.device)
         dtxt = torch.empty((B, T, D), dtype=torch.bfloat16, device=dx0.device) if self.text_proj else None
         it = self.image_tokenizer
+        pad = st.get("pad")
+        if pad is not None:
+            # pad masks: d(pos_embedding) from the full dx0 first (the position embedding IS used
+            # in the masked rows), then those rows are zeroed, and only then does anything else
+            # read dx0: no gradient reaches a tokenizer through a masked token
+            K.colsum(dx0.view(B, self.L0 * D), self.pos_embed.grad.view(-1))
+            K.pad_mask_rows_bwd(dx0, self.layer_sets[0][1], pad[0], pad[1], self.text_set)
         # token gradients (and the readout embedding's); the image row / column position
         # embedding gradients by token window (mmt_patch_embed_grad)
         _C.call("mmt_seq_assemble_bwd", B, self.L0, D, _C.ptr(self.row_src), _C.ptr(dx0),
@@ -841,7 +927,8 @@ class Octo:
                     self.cfg.patch_size, it.Q, _C.ptr(self.img_rows), _C.ptr(dx0),
                     _C.ptr(st["rt"]), _C.ptr(st["ct"]), _C.ptr(it.row_emb.grad),
                     _C.ptr(it.col_emb.grad), _C.stream_ptr())
-        K.colsum(dx0.view(B, self.L0 * D), self.pos_embed.grad.view(-1))
+        if pad is None:
+            K.colsum(dx0.view(B, self.L0 * D), self.pos_embed.grad.view(-1))
         if self.value_tokenizer is not None:
             self.value_tokenizer.backward(dx0, st["val_tok"], self.value_rows)
         if self.point_cloud_tokenizer is not None:
@@ -1188,41 +1275,51 @@ def _train_step(loss_fn, model: Octo, train_state: OCTOTrainState, text_tokens, 
     return train_state, grads_tree(model)
 
 
-def _step_kw(action_pad_mask, values, point_clouds=None) -> dict:
+def _step_kw(action_pad_mask, values, point_clouds=None, set_pad_mask=None,
+             text_pad_mask=None) -> dict:
     """The optional keywords of a loss, passed only when given."""
     kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
     if values is not None:
         kw["values"] = values
     if point_clouds is not None:
         kw["point_clouds"] = point_clouds
+    if set_pad_mask is not None:
+        kw["set_pad_mask"] = set_pad_mask
+    if text_pad_mask is not None:
+        kw["text_pad_mask"] = text_pad_mask
     return kw
 
 
 def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                          action_pad_mask=None, values=None, point_clouds=None):
+                          action_pad_mask=None, values=None, point_clouds=None,
+                          set_pad_mask=None, text_pad_mask=None):
     """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_l2_loss's."""
-    kw = _step_kw(action_pad_mask, values, point_clouds)
+    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_l2_loss's;
+    set_pad_mask, text_pad_mask: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
     return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
-                           action_pad_mask=None, values=None, point_clouds=None):
+                           action_pad_mask=None, values=None, point_clouds=None,
+                           set_pad_mask=None, text_pad_mask=None):
     """Reference octo.py:282-320: value_and_grad of mean(compute_ce_loss), apply_gradients,
-    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_ce_loss's."""
-    kw = _step_kw(action_pad_mask, values, point_clouds)
+    metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_ce_loss's;
+    set_pad_mask, text_pad_mask: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
     return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
                          inject: Optional[dict] = None, action_pad_mask=None, values=None,
-                         point_clouds=None):
+                         point_clouds=None, set_pad_mask=None, text_pad_mask=None):
     """Reference octo.py:204-240: value_and_grad of the denoise loss, apply_gradients, metrics
     merge. Returns (train_state, grads) like the reference; grads are views of the flat gradient
     buffer by parameter name, the loss is train_state.last_loss (device) and the running average
-    train_state.metrics. action_pad_mask, values: compute_diffusion_denoise_loss's."""
-    kw = _step_kw(action_pad_mask, values, point_clouds)
+    train_state.metrics. action_pad_mask, values: compute_diffusion_denoise_loss's;
+    set_pad_mask, text_pad_mask: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
     return _train_step(model.compute_diffusion_denoise_loss, model, train_state, text_tokens,
                        images, actions, inject=inject, **kw)

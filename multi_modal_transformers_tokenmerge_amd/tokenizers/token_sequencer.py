@@ -288,6 +288,16 @@ class TokenSequence:
             mods.append(q.modality)
         return LayerSets(starts, lens, vis, causal, mods)
 
+    def pad_mask_layout(self):
+        """What the observation pad masks need of the sequence: (the set count after the repeat
+        expansion = the second dimension of set_pad_mask, the bit mask of the Readout sets, which
+        cannot be absent, and the index of the first text-class set, the one text_pad_mask
+        speaks of, -1 without one)."""
+        seq = self.token_sequence
+        readout_bits = sum(1 << i for i, ts in enumerate(seq) if isinstance(ts, Readout))
+        text_set = next((i for i, ts in enumerate(seq) if isinstance(ts, Text)), -1)
+        return len(seq), readout_bits, text_set
+
     def num_layers_until_empty(self) -> int:
         return min((ts.num_tokens // ts.tokens_compressed_per_layer
                     for ts in self.token_sequence if ts.tokens_compressed_per_layer), default=10 ** 9)
