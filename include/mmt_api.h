@@ -49,15 +49,18 @@ int mmt_version(void);
  * arrays (mmt_tome_merge_wavg_fwd / _bwd, mmt_tome_merge_seqnorm_fwd, mmt_ln_unmerge_dropout_bwd,
  * mmt_gather_rows, mmt_topk_scatter_bwd, mmt_tome_pos_map, mmt_tome_source_step / _groups,
  * mmt_tome_unmerge_fwd / _bwd, mmt_value_tokens_fwd / _bwd, mmt_pc_sample_group,
- * mmt_pc_embed_fwd / _bwd, mmt_pad_mask_pack) cannot see those device values at
- * launch. Their kernels
+ * mmt_pc_sample_group_counts, mmt_pc_embed_fwd / _bwd, mmt_pad_mask_pack,
+ * mmt_pad_mask_pack_counts) cannot see those device values at launch. mmt_depth_unproject takes
+ * no index, but sizes its output from device data: every slot it writes is in [0, P). Their kernels
  * range-check every index they use; an invalid one is replaced by 0 (so no access leaves its
  * tensor and the context survives) and sets a bit of a library-wide device status word:
  *   MMT_FAULT_TOME_INDEX     unm / src not in [0, ceil(t/2)), dst not in [0, t/2)
  *   MMT_FAULT_TOME_PARTITION unm and src repeat an a-token (not a partition of the a half)
  *   MMT_FAULT_POS_MAP        pos_map entry not in [0, t - r)
  *   MMT_FAULT_ROW_INDEX      gathered / scattered row not in [0, L); a saved value token not in
- *                            [0, num_bins) (mmt_value_tokens_bwd: the entry is skipped)
+ *                            [0, num_bins) (mmt_value_tokens_bwd: the entry is skipped); a cloud's
+ *                            count not in [0, P] or an injected start not below the count
+ *                            (mmt_pc_sample_group_counts: clamped / 0)
  *   MMT_FAULT_PAD_MASK       a Readout set flagged absent in a set pad mask (mmt_pad_mask_pack:
  *                            the set is treated as present)
  * mmt_device_status synchronises `stream`, returns MMT_OK if the word is clear, else clears it and
@@ -541,6 +544,17 @@ int mmt_tome_size_bias(const float* size, int B, int t, int set_start, int L, fl
  * (MMT_FAULT_PAD_MASK, mmt_device_status) and treated as present, so its bit is set. */
 int mmt_pad_mask_pack(const uint8_t* set_mask, int B, int n_sets, uint32_t readout_bits,
                       uint32_t* words, mmt_stream_t stream);
+/* Thin clouds become absent sets: words[b] = mmt_pad_mask_pack's result (set_mask NULL: every set
+ * present, no Readout rule to apply) with bit pc_set[s] cleared where counts[b, s] <
+ * min_points[s]. counts: int32 (B, S) on the DEVICE, the valid points of the S clouds of a sample
+ * (mmt_depth_unproject's, or the caller's); pc_set, min_points: HOST arrays of S entries, the token
+ * set of cloud s (in [0, n_sets), not a Readout set) and its token count n (a cloud with fewer
+ * points than tokens is absent; min_points >= 0). 1 <= S <= n_sets. No host synchronisation: a
+ * replayed graph follows new contents of counts. Counts say nothing about cameras:
+ * mmt_pad_mask_images is for a caller's own set mask. */
+int mmt_pad_mask_pack_counts(const uint8_t* set_mask, int B, int n_sets, uint32_t readout_bits,
+                             const int32_t* counts, int S, const int32_t* pc_set,
+                             const int32_t* min_points, uint32_t* words, mmt_stream_t stream);
 /* dst = src (B, I, image_bytes: the camera images, any pixel type) with the image_bytes of
  * image (b, i) zeroed where set image_set[i] (HOST array of I set indices in [0, n_sets)) is
  * absent in words[b]. src is not changed; src != dst, both 16-B aligned, image_bytes a multiple of
@@ -888,6 +902,26 @@ int mmt_pc_sample_group(const float* points, int64_t ld_b, int64_t ld_s, int B, 
                         int n, int k, const int32_t* start, const uint32_t* rng,
                         int64_t sample_offset, int32_t* centroid_idx, int32_t* neighbour_idx,
                         mmt_stream_t stream);
+/* Ragged clouds: counts int32 (B S) on the device, c = counts[b S + s] = the number of leading
+ * rows of cloud (b, s) that are points; NULL = mmt_pc_sample_group (every cloud has P points, the
+ * same kernel instantiation, launches and bits). P stays the row stride and the limit above.
+ *   count    outside [0, P]: clamped into it, MMT_FAULT_ROW_INDEX
+ *   rows >= c are never read: their contents (NaN and Inf included) influence no output
+ *   start    injected: start >= c gives 0 and MMT_FAULT_ROW_INDEX (any start when c == 0); drawn:
+ *            (draw_u32(...) * c) >> 32, 0 when c == 0; else 0
+ *   sampling the rule above over the rows < c for i < min(n, c); for i >= c >= 1 ids[i] =
+ *            ids[i - c] (periodic repeat); c == 0: every index 0
+ *   grouping the min(k, c) nearest among the rows < c, ascending by (d, index); the slots r >= c
+ *            repeat slot 0, the nearest point (the centroid itself or its lowest-index duplicate,
+ *            d = 0): the PointNet++ "pad with the first" convention; c == 0: every index 0
+ * Every index written is in [0, max(c, 1)). mmt_pc_embed_fwd / _bwd take these indices unchanged:
+ * the max over the neighbours records the FIRST slot that attains it, so a repeated slot changes
+ * neither the pooled value nor the arg-max and receives no gradient. A cloud with c < n gives
+ * repeated tokens; Octo treats it as an absent set (mmt_pad_mask_pack_counts). */
+int mmt_pc_sample_group_counts(const float* points, int64_t ld_b, int64_t ld_s, int B, int S, int P,
+                               int C, int n, int k, const int32_t* start, const uint32_t* rng,
+                               int64_t sample_offset, const int32_t* counts, int32_t* centroid_idx,
+                               int32_t* neighbour_idx, mmt_stream_t stream);
 /* Forward of the embedding: writes x0[b, rows[s n + m], :] for token m of cloud (b, s) and no
  * other row (mmt_seq_assemble_fwd skips the rows of kind 4, which these are), and argmax
  * (B, S, n, F2) uint8, the first neighbour slot that attains each maximum. rows (S n,) int32; pe
@@ -916,6 +950,33 @@ int mmt_pc_embed_bwd(const void* dx0, int64_t xs_b, int64_t xs_t, const int32_t*
                      const float* w2, const float* b2, const float* w_out, float* dw1, float* db1,
                      float* dw2, float* db2, float* dw_out, float* db_out, void* workspace,
                      int64_t workspace_bytes, mmt_stream_t stream);
+
+/* ------------------------------------------------------------------ depth back-projection
+ * A depth image (H, W) with pinhole intrinsics as a point cloud of at most P points and its count
+ * (csrc/depth.hip), the input of mmt_pc_sample_group_counts. depth: (B, S, H, W) contiguous, uint16
+ * (depth_is_f32 == 0; millimetres with depth_scale 0.001) or fp32; intrinsics fp32 (B, S, 4) =
+ * fx fy cx cy; pose fp32 (B, S, 3, 4) = [R | t] camera -> base, row-major, NULL: the camera frame;
+ * rgb uint8 (B, S, H, W, 3) or NULL; points fp32 (B, S, P, C) contiguous, C = 6 with rgb, else 3;
+ * counts int32 (B, S). Every operation is individually rounded (numpy float32 restates the bits):
+ *   z      = fmul(float(d), depth_scale)
+ *   valid  uint16: d != 0; fp32: d > 0 and finite (a NaN is invalid); both: z_min <= z <= z_max
+ *   x      = fdiv(fmul(fsub(float(u), cx), z), fx), y likewise from the row v, cy, fy
+ *   pose   p'_i = fadd(fadd(fadd(fmul(R_i0, x), fmul(R_i1, y)), fmul(R_i2, z)), t_i)
+ *   colour features 3 .. 5 = fdiv(float(channel), 255.f)
+ *   selection: the V valid pixels are ranked in raster order, j = 0 .. V-1. V <= P: slot j holds
+ *          rank j. Else slot q holds the pixel of rank ceil(q V / P) (in 64-bit integers): an evenly
+ *          strided subsample, exactly P slots, strictly increasing ranks, slot 0 = rank 0.
+ *   counts = min(V, P); the slots >= counts are written as zeros in all C features.
+ * One writer per slot; the result does not depend on scheduling. MMT_ERR_INVALID before a launch:
+ * P outside 1 .. MMT_PC_MAX_POINTS, H W > 2^20, depth not 16-B aligned or H W no multiple of 8
+ * (uint16) / 4 (fp32) (images are read as 16-B vectors), depth_scale <= 0, z_min > z_max, a NaN
+ * among the three. fx and fy are device data and cannot be checked at launch: with a zero or
+ * non-finite one the coordinates are unspecified (Inf / NaN), every write still inside points and
+ * counts, the selection and counts unaffected. */
+int mmt_depth_unproject(const void* depth, int depth_is_f32, int B, int S, int H, int W,
+                        const float* intrinsics, const float* pose, const uint8_t* rgb,
+                        float depth_scale, float z_min, float z_max, int P, float* points,
+                        int32_t* counts, mmt_stream_t stream);
 
 /* ------------------------------------------------------------------ QK-norm
  * flax.linen.SelfAttention(normalize_qk=True): LayerNorm(use_bias=False) over the head dimension of

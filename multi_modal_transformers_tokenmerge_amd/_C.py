@@ -69,6 +69,7 @@ SIGNATURES: dict[str, list] = {
                              L, L, P, P, L, P],
     "mmt_tome_size_bias": [P, I, I, I, I, P, L, I, P],
     "mmt_pad_mask_pack": [P, I, I, U32, P, P],
+    "mmt_pad_mask_pack_counts": [P, I, I, U32, P, I, P, P, P, P],
     "mmt_pad_mask_images": [P, P, I, I, I, L, P, P, P],
     "mmt_pad_mask_bias": [P, I, I, I, P, P, P, I, I, P, L, I, P],
     "mmt_pad_mask_rows_fwd": [P, I, I, I, I, P, P, P, I, I, P, P, L, L, P],
@@ -94,6 +95,8 @@ SIGNATURES: dict[str, list] = {
     "mmt_value_tokens_fwd": [P, L, I, I, I, F, I, P, P, P, I, P, L, L, P, P],
     "mmt_value_tokens_bwd": [P, L, L, I, I, P, P, I, I, P, P],
     "mmt_pc_sample_group": [P, L, L, I, I, I, I, I, I, P, P, L, P, P, P],
+    "mmt_pc_sample_group_counts": [P, L, L, I, I, I, I, I, I, P, P, L, P, P, P, P],
+    "mmt_depth_unproject": [P, I, I, I, I, I, P, P, P, F, F, F, I, P, P, P],
     "mmt_pc_embed_fwd": [P, L, L, I, I, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P, P, I, P, L, L, P,
                          P],
     "mmt_pc_embed_bwd_workspace": [I, I, I, I, I, I, I],
@@ -358,6 +361,7 @@ VALUE_MIN_BINS, VALUE_MAX_BINS = 2, 4096
 PC_MAX_POINTS, PC_MAX_TOKENS, PC_MAX_NEIGHBOURS = 4096, 256, 32
 PC_MIN_FEATURES, PC_MAX_FEATURES, PC_MAX_WIDTH = 3, 8, 4096
 PC_HIDDEN_WIDTHS = (32, 64, 128)
+DEPTH_MAX_PIXELS = 1 << 20           # mmt_depth_unproject: H * W at most
 QK_NORM_WIDTHS = (32, 64, 128, 256)   # head widths of mmt_qk_norm_fwd / _bwd
 HEAD_LOSS_MSE, HEAD_LOSS_L1 = 0, 1   # MMT_HEAD_LOSS_* (mmt_head_continuous loss_kind)
 DECODE_ARGMAX, DECODE_SAMPLE = 0, 1  # MMT_DECODE_* (mmt_head_categorical_decode mode)

@@ -717,6 +717,46 @@ def pad_mask_pack(set_mask: torch.Tensor, readout_bits: int = 0,
     return out
 
 
+def pad_mask_pack_counts(set_mask: torch.Tensor | None, n_sets: int, readout_bits: int,
+                         counts: torch.Tensor, pc_sets, min_points,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """pad_mask_pack with thin clouds as absent sets (mmt_pad_mask_pack_counts): bit pc_sets[s]
+    of words[b] is cleared where counts[b, s] < min_points[s]. set_mask: bool (B, n_sets) or None
+    (every set present); counts: int32 (B, S) on the device, read by the kernel (no host
+    synchronisation: a replayed graph follows its contents); pc_sets, min_points: S host
+    integers, the token set of each cloud and the points it needs (its token count)."""
+    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 2 or \
+            not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 (B, S) tensor")
+    _dev(set_mask, counts, out)
+    B, S = counts.shape
+    pc_sets, min_points = [int(v) for v in pc_sets], [int(v) for v in min_points]
+    if len(pc_sets) != S or len(min_points) != S:
+        raise ValueError(f"pc_sets and min_points must name the {S} clouds of counts, got "
+                         f"{len(pc_sets)} and {len(min_points)}")
+    if not 1 <= n_sets <= _C.PAD_MASK_MAX_SETS or not 1 <= S <= n_sets:
+        raise ValueError(f"n_sets must be in 1 .. {_C.PAD_MASK_MAX_SETS} and S in 1 .. n_sets, "
+                         f"got {n_sets} and {S}")
+    for s, m in zip(pc_sets, min_points):
+        if not 0 <= s < n_sets or (readout_bits >> s) & 1 or m < 0:
+            raise ValueError(f"a cloud's set must be in [0, {n_sets}) and no Readout set, its "
+                             f"min_points >= 0, got set {s}, min_points {m}")
+    if set_mask is not None and (set_mask.dim() != 2 or set_mask.dtype != torch.bool
+                                 or tuple(set_mask.shape) != (B, n_sets)
+                                 or not set_mask.is_contiguous()
+                                 or set_mask.device != counts.device):
+        raise ValueError(f"set_mask must be a contiguous bool ({B}, {n_sets}) tensor on the "
+                         "counts' device")
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int32, device=counts.device)
+    elif tuple(out.shape) != (B,) or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous int32 ({B},)")
+    arr = _C.ctypes.c_int32 * S
+    _C.call("mmt_pad_mask_pack_counts", ptr(set_mask), B, n_sets, readout_bits, ptr(counts), S,
+            arr(*pc_sets), arr(*min_points), ptr(out), _C.stream_ptr())
+    return out
+
+
 def pad_mask_images(images: torch.Tensor, words: torch.Tensor, image_sets, n_sets: int,
                     out: torch.Tensor | None = None) -> torch.Tensor:
     """A copy of the camera images (B, I, H, W, C), uint8 or fp32, contiguous, with the pixels of
@@ -1334,21 +1374,94 @@ def _pc_points(points: torch.Tensor):
 
 
 def pc_sample_group(points: torch.Tensor, n: int, k: int, start: torch.Tensor | None = None,
-                    rng: torch.Tensor | None = None, sample_offset: int = 0):
+                    rng: torch.Tensor | None = None, sample_offset: int = 0,
+                    counts: torch.Tensor | None = None):
     """Farthest-point sampling and kNN grouping of every cloud of points (B, S, P, C) fp32
     (mmt_pc_sample_group): (centroid_idx (B, S, n), neighbour_idx (B, S, n, k)) int32. The first
     centroid: start (B, S) int32 if given, else drawn from rng (the two-word RNG state) for the
-    global cloud index (sample_offset + b) * S + s, else point 0."""
-    _dev(points, start, rng)
+    global cloud index (sample_offset + b) * S + s, else point 0. counts (B, S) int32: ragged
+    clouds, the leading counts[b, s] rows of a cloud are its points and the rest is never read
+    (mmt_pc_sample_group_counts: centroids repeat periodically past the count, neighbour slots
+    past it repeat slot 0; a count outside [0, P] or a start not below it: device_status())."""
+    _dev(points, start, rng, counts)
     B, S, P, C, ld_b, ld_s = _pc_points(points)
     check_pc_limits(P, C, n, k)
     if start is not None:
         _check_i32(start, (B, S), "start")
+    if counts is not None:
+        if not torch.is_tensor(counts) or counts.device != points.device:
+            raise ValueError("counts must be an int32 tensor on the points' device")
+        _check_i32(counts, (B, S), "counts")
     cidx = torch.empty((B, S, n), dtype=torch.int32, device=points.device)
     nidx = torch.empty((B, S, n, k), dtype=torch.int32, device=points.device)
-    _C.call("mmt_pc_sample_group", ptr(points), ld_b, ld_s, B, S, P, C, n, k, ptr(start), ptr(rng),
-            int(sample_offset), ptr(cidx), ptr(nidx), _C.stream_ptr())
+    if counts is None:
+        _C.call("mmt_pc_sample_group", ptr(points), ld_b, ld_s, B, S, P, C, n, k, ptr(start),
+                ptr(rng), int(sample_offset), ptr(cidx), ptr(nidx), _C.stream_ptr())
+    else:
+        _C.call("mmt_pc_sample_group_counts", ptr(points), ld_b, ld_s, B, S, P, C, n, k, ptr(start),
+                ptr(rng), int(sample_offset), ptr(counts), ptr(cidx), ptr(nidx), _C.stream_ptr())
     return cidx, nidx
+
+
+def depth_unproject(depth: torch.Tensor, intrinsics: torch.Tensor, num_points: int,
+                    depth_scale: float = 0.001, z_min: float = 0.1, z_max: float = 3.0,
+                    pose: torch.Tensor | None = None, rgb: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None, counts: torch.Tensor | None = None):
+    """Depth images (B, S, H, W), uint16 or fp32, contiguous -> (points fp32 (B, S, P, C),
+    counts int32 (B, S)) (mmt_depth_unproject): the valid pixels back-projected with intrinsics
+    fp32 (B, S, 4) = fx fy cx cy, moved by pose fp32 (B, S, 3, 4) if given, coloured by rgb uint8
+    (B, S, H, W, 3) if given (C = 6, else 3); at most P = num_points of them, evenly strided in
+    raster order; the slots past counts are zeros. ValueError before any launch: dtypes, shapes,
+    devices, 1 <= P <= 4096, H W <= 2^20 and a multiple of 8 (uint16) / 4 (fp32), depth_scale > 0,
+    z_min <= z_max. fx, fy (device data) must be non-zero: the coordinates are unspecified else."""
+    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.dtype not in (torch.uint16,
+                                                                             torch.float32):
+        raise ValueError("depth must be a uint16 or fp32 (B, S, H, W) tensor")
+    if not depth.is_cuda:
+        raise ValueError("depth must live on the GPU")
+    _dev(depth, intrinsics, pose, rgb, out, counts)
+    B, S, H, W = depth.shape
+    f32 = depth.dtype == torch.float32
+    if isinstance(num_points, bool) or not isinstance(num_points, int) or \
+            not 1 <= num_points <= _C.PC_MAX_POINTS:
+        raise ValueError(f"num_points must be an integer in 1 .. {_C.PC_MAX_POINTS}, "
+                         f"got {num_points!r}")
+    if B < 1 or S < 1 or H < 1 or W < 1 or H * W > _C.DEPTH_MAX_PIXELS:
+        raise ValueError(f"depth {tuple(depth.shape)}: need B, S, H, W >= 1 and H * W <= "
+                         f"{_C.DEPTH_MAX_PIXELS}")
+    epv = 4 if f32 else 8
+    if not depth.is_contiguous() or (H * W) % epv or depth.data_ptr() % 16:
+        raise ValueError(f"depth must be contiguous and 16-B aligned with H * W a multiple of "
+                         f"{epv} (images are read as 16-B vectors), got H * W = {H * W}")
+    depth_scale, z_min, z_max = float(depth_scale), float(z_min), float(z_max)
+    if not depth_scale > 0.0 or not z_min <= z_max:
+        raise ValueError(f"need depth_scale > 0 and z_min <= z_max, got {depth_scale}, "
+                         f"({z_min}, {z_max})")
+    for t, shape, dt, what in ((intrinsics, (B, S, 4), torch.float32, "intrinsics"),
+                               (pose, (B, S, 3, 4), torch.float32, "pose"),
+                               (rgb, (B, S, H, W, 3), torch.uint8, "rgb")):
+        if t is None and what != "intrinsics":
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or \
+                not t.is_contiguous() or t.device != depth.device:
+            raise ValueError(f"{what} must be a contiguous {dt} {shape} tensor on the depth's "
+                             "device")
+    C = 6 if rgb is not None else 3
+    P = num_points
+    if out is None:
+        out = torch.empty((B, S, P, C), dtype=torch.float32, device=depth.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, S, P, C) or \
+            not out.is_contiguous() or out.device != depth.device:
+        raise ValueError(f"out must be contiguous fp32 {(B, S, P, C)} on the depth's device")
+    if counts is None:
+        counts = torch.empty((B, S), dtype=torch.int32, device=depth.device)
+    elif counts.device != depth.device:
+        raise ValueError("counts must live on the depth's device")
+    else:
+        _check_i32(counts, (B, S), "counts")
+    _C.call("mmt_depth_unproject", ptr(depth), int(f32), B, S, H, W, ptr(intrinsics), ptr(pose),
+            ptr(rgb), depth_scale, z_min, z_max, P, ptr(out), ptr(counts), _C.stream_ptr())
+    return out, counts
 
 
 def _pc_weights(C: int, w1, b1, w2, b2, w_out, b_out):

@@ -6,6 +6,8 @@
 // The attention kernels are not touched: the mask enters them as the key_bias of
 // mmt_attn_fwd_keybias / mmt_attn_bwd_keybias, MMT_PAD_MASK_LOGIT on the masked keys.
 //   pack      bool (B, n_sets) -> one word of present-bits per sample (Readout sets forced present)
+//   pack_counts  the same, with the bit of a PointCloud set cleared where the sample's cloud has
+//             fewer valid points than the set has tokens (counts are read on the device)
 //   bias      the key_bias rows of one layer from the words, the layer's set table and the text mask
 //   images    a copy of the camera images with the pixels of absent cameras zeroed (the stem's
 //             GroupNorm runs over all patches of all cameras of a sample)
@@ -50,6 +52,36 @@ __global__ void pad_mask_pack_kernel(const uint8_t* __restrict__ mask, int B, in
     record_fault(fault, MMT_FAULT_PAD_MASK);
     w |= readout_bits;
   }
+  words[b] = w;
+}
+
+struct CountSets {
+  int S;
+  int set[MMT_PAD_MASK_MAX_SETS];
+  int min_points[MMT_PAD_MASK_MAX_SETS];
+};
+
+// pack, then bit cs.set[s] cleared where counts[b, s] < cs.min_points[s]. mask NULL: all present.
+__global__ void pad_mask_pack_counts_kernel(const uint8_t* __restrict__ mask, int B, int n_sets,
+                                            uint32_t readout_bits, CountSets cs,
+                                            const int32_t* __restrict__ counts,
+                                            uint32_t* __restrict__ words, unsigned int* fault) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  uint32_t w = 0;
+  if (mask == nullptr) {
+    w = n_sets >= 32 ? 0xffffffffu : (1u << n_sets) - 1u;
+  } else {
+    for (int s = 0; s < n_sets; ++s)
+      if (mask[(int64_t)b * n_sets + s]) w |= 1u << s;
+    if (~w & readout_bits) {  // a Readout set flagged absent: reported, treated as present
+      record_fault(fault, MMT_FAULT_PAD_MASK);
+      w |= readout_bits;
+    }
+  }
+#pragma unroll 1
+  for (int s = 0; s < cs.S; ++s)
+    if (counts[(int64_t)b * cs.S + s] < cs.min_points[s]) w &= ~(1u << cs.set[s]);
   words[b] = w;
 }
 
@@ -189,6 +221,35 @@ extern "C" int mmt_pad_mask_pack(const uint8_t* set_mask, int B, int n_sets, uin
   hipLaunchKernelGGL(pad_mask_pack_kernel, dim3((B + 255) / 256), dim3(256), 0, as_stream(stream),
                      set_mask, B, n_sets, readout_bits, words, fault_word());
   MMT_CHECK_LAUNCH("mmt_pad_mask_pack");
+  return MMT_OK;
+}
+
+extern "C" int mmt_pad_mask_pack_counts(const uint8_t* set_mask, int B, int n_sets,
+                                        uint32_t readout_bits, const int32_t* counts, int S,
+                                        const int32_t* pc_set, const int32_t* min_points,
+                                        uint32_t* words, mmt_stream_t stream) {
+  const char* fn = "mmt_pad_mask_pack_counts";
+  MMT_CHECK_ARG(counts && pc_set && min_points && words, "%s: null pointer", fn);
+  MMT_CHECK_ARG(B > 0, "%s: B must be > 0", fn);
+  MMT_CHECK_ARG(n_sets >= 1 && n_sets <= MMT_PAD_MASK_MAX_SETS, "%s: n_sets %d outside 1 .. %d", fn,
+                n_sets, MMT_PAD_MASK_MAX_SETS);
+  MMT_CHECK_ARG((readout_bits >> n_sets) == 0, "%s: readout_bits 0x%x names a set past the %d sets",
+                fn, readout_bits, n_sets);
+  MMT_CHECK_ARG(S >= 1 && S <= n_sets, "%s: S %d outside 1 .. n_sets = %d", fn, S, n_sets);
+  CountSets cs{};
+  cs.S = S;
+  for (int s = 0; s < S; ++s) {
+    MMT_CHECK_ARG(pc_set[s] >= 0 && pc_set[s] < n_sets && !((readout_bits >> pc_set[s]) & 1u),
+                  "%s: cloud %d belongs to set %d, outside the %d sets or a Readout set", fn, s,
+                  pc_set[s], n_sets);
+    MMT_CHECK_ARG(min_points[s] >= 0, "%s: min_points[%d] = %d is negative", fn, s, min_points[s]);
+    cs.set[s] = pc_set[s];
+    cs.min_points[s] = min_points[s];
+  }
+  hipLaunchKernelGGL(pad_mask_pack_counts_kernel, dim3((B + 255) / 256), dim3(256), 0,
+                     as_stream(stream), set_mask, B, n_sets, readout_bits, cs, counts, words,
+                     fault_word());
+  MMT_CHECK_LAUNCH(fn);
   return MMT_OK;
 }
 

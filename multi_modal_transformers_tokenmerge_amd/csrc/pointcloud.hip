@@ -10,6 +10,8 @@
 //   index on ties), cross-wave arg-max through a double-buffered LDS slot with ONE barrier.
 //   Grouping in the same launch: one wave per centroid holds the packed (d, index) keys of the
 //   whole cloud in registers and takes k wave arg-mins, each over the keys above the last one.
+//   mmt_pc_sample_group_counts: the same kernel's RAGGED instantiation, the leading counts[cloud]
+//   rows of a cloud are its points (centroids repeat past the count, neighbour slots repeat slot 0).
 // mmt_pc_embed_fwd: a group of F2 threads per token (thread = output column of layer 2, the k
 //   neighbours in its registers, so the max over neighbours needs no exchange), two groups per
 //   workgroup, 8 tokens per workgroup, W1 staged in LDS; the output Dense then runs for the 8
@@ -29,7 +31,11 @@ namespace {
 
 typedef unsigned long long u64;
 
-// d(p, c): every operation individually rounded, so no FMA contraction (numpy float32 restates it)
+// d(p, c): every operation individually rounded, so no FMA contraction (numpy float32 restates it).
+// The __f*_rn intrinsics are plain operators in the HIP headers, and -ffp-contract=fast ignores
+// `#pragma clang fp contract(off)`: compiled that way this became fma(dz, dz, dx dx) + dy dy, and
+// two neighbours whose distances lie a rounding apart could change places against the restatement.
+// So csrc/build.py compiles this file with -ffp-contract=off (every FMA in it is an explicit fmaf).
 __device__ __forceinline__ float dist3(float px, float py, float pz, float cx, float cy, float cz) {
   const float dx = __fsub_rn(px, cx), dy = __fsub_rn(py, cy), dz = __fsub_rn(pz, cz);
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
@@ -55,12 +61,20 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v) {
   return v;
 }
 
-// PPT points per thread in the sampling phase (P <= 256 * PPT), 4 * PPT per lane in the grouping
-template <int PPT>
+// PPT points per thread in the sampling phase (P <= 256 * PPT), 4 * PPT per lane in the grouping.
+// RAGGED: counts[cloud] = c leading rows are points (clamped into [0, P]; outside:
+// MMT_FAULT_ROW_INDEX); the rows >= c are never loaded. P stays the row stride and the sizing.
+// Every `idx < Pv` below is `idx < P` in the instantiation without counts.
+//   start    an injected start >= c: 0 and MMT_FAULT_ROW_INDEX; the draw is (u32 * c) >> 32
+//   sampling the rule above over the rows < c for i < min(n, c); ids[i] = ids[i - c] past it
+//   grouping the min(k, c) nearest among the rows < c; the slots r >= c repeat slot 0
+//   c == 0   every index 0
+template <int PPT, bool RAGGED>
 __global__ __launch_bounds__(256) void pc_sample_group_kernel(
     const float* __restrict__ points, int64_t ld_b, int64_t ld_s, int S, int P, int C, int n, int k,
     const int32_t* __restrict__ start, const uint32_t* __restrict__ rng, int64_t sample_offset,
-    int32_t* __restrict__ cidx, int32_t* __restrict__ nidx, unsigned int* fault) {
+    const int32_t* __restrict__ counts, int32_t* __restrict__ cidx, int32_t* __restrict__ nidx,
+    unsigned int* fault) {
   extern __shared__ __align__(16) unsigned char pc_smem[];
   u64* red = reinterpret_cast<u64*>(pc_smem);            // [2][4]
   int* cid = reinterpret_cast<int*>(pc_smem + 64);       // [n] (n <= 256)
@@ -71,13 +85,30 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
   const int cloud = blockIdx.x, b = cloud / S, s = cloud - b * S;
   const float* base = points + (int64_t)b * ld_b + (int64_t)s * ld_s;
 
+  int Pv = P;  // the rows that are points; block-uniform
+  if (RAGGED) {
+    Pv = counts[cloud];
+    if ((unsigned)Pv > (unsigned)P) {
+      Pv = Pv < 0 ? 0 : P;
+      if (tid == 0) record_fault(fault, MMT_FAULT_ROW_INDEX);
+    }
+    if (Pv == 0) {  // an empty cloud: every index 0 (a start, any start, is outside it)
+      if (start != nullptr && tid == 0) record_fault(fault, MMT_FAULT_ROW_INDEX);
+      for (int e = tid; e < n; e += 256) cidx[(int64_t)cloud * n + e] = 0;
+      for (int e = tid; e < n * k; e += 256) nidx[(int64_t)cloud * n * k + e] = 0;
+      return;
+    }
+  }
+  const int ns = RAGGED ? min(n, Pv) : n;  // sampled centroids, the rest repeat them
+  const int kk = RAGGED ? min(k, Pv) : k;  // searched neighbours, the rest repeat slot 0
+
   float px[PPT], py[PPT], pz[PPT], dist[PPT];
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
     const int idx = j * 256 + tid;
     px[j] = py[j] = pz[j] = 0.f;
     dist[j] = INFINITY;
-    if (idx < P) {
+    if (idx < Pv) {
       const float* p = base + (int64_t)idx * C;
       px[j] = p[0], py[j] = p[1], pz[j] = p[2];
       sx[idx] = px[j], sy[idx] = py[j], sz[idx] = pz[j];
@@ -86,14 +117,14 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
   int last = 0;
   if (start != nullptr) {
     last = start[cloud];
-    if ((unsigned)last >= (unsigned)P) {
+    if ((unsigned)last >= (unsigned)Pv) {
       last = 0;
       if (tid == 0) record_fault(fault, MMT_FAULT_ROW_INDEX);
     }
   } else if (rng != nullptr) {
     const uint32_t key = stream_key(rng[0], rng[1], 0xFFF7u, 1u);
     const uint32_t g = (uint32_t)((sample_offset + b) * S + s);
-    last = (int)(((u64)draw_u32(key, g) * (u64)P) >> 32);
+    last = (int)(((u64)draw_u32(key, g) * (u64)Pv) >> 32);
   }
   if (tid == 0) {
     cid[0] = last;
@@ -101,13 +132,13 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
   }
   __syncthreads();
 
-  for (int i = 1; i < n; ++i) {
+  for (int i = 1; i < ns; ++i) {
     const float cx = sx[last], cy = sy[last], cz = sz[last];
     u64 best = 0;
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
       const int idx = j * 256 + tid;
-      if (idx < P) {
+      if (idx < Pv) {
         // a sampled point holds -1 from here on: fminf(-1, d) = -1 for every d >= 0 and for NaN
         const float d = idx == last ? -1.f
                                     : fminf(dist[j], dist3(px[j], py[j], pz[j], cx, cy, cz));
@@ -125,13 +156,21 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
 #pragma unroll
     for (int w = 1; w < 4; ++w) m = slot[w] > m ? slot[w] : m;
     last = (int)(0xFFFFFFFFu - (uint32_t)m);
-    if ((unsigned)last >= (unsigned)P) last = 0;  // unreachable for n <= P; never out of bounds
+    if ((unsigned)last >= (unsigned)Pv) last = 0;  // unreachable for n <= P; never out of bounds
     if (tid == 0) {
       cid[i] = last;
       cidx[(int64_t)cloud * n + i] = last;
     }
   }
   __syncthreads();
+  if (RAGGED && ns < n) {  // ids[i] = ids[i - c] = ids[i mod c]: n <= 256, one thread per slot
+    if (tid >= ns && tid < n) {
+      const int v = cid[tid % ns];
+      cid[tid] = v;
+      cidx[(int64_t)cloud * n + tid] = v;
+    }
+    __syncthreads();
+  }
 
   // grouping: wave per centroid, the k smallest (d, index) in ascending order
   constexpr int PPL = PPT * 4;
@@ -143,12 +182,13 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
     for (int j = 0; j < PPL; ++j) {
       const int idx = j * 64 + lane;
       key[j] = ~0ull;
-      if (idx < P)
+      if (idx < Pv)
         key[j] = ((u64)__float_as_uint(dist3(sx[idx], sy[idx], sz[idx], cx, cy, cz)) << 32) |
                  (uint32_t)idx;
     }
     u64 lastk = 0;
-    for (int r = 0; r < k; ++r) {
+    int first = 0;
+    for (int r = 0; r < kk; ++r) {
       u64 loc = ~0ull;
 #pragma unroll
       for (int j = 0; j < PPL; ++j) {
@@ -158,9 +198,12 @@ __global__ __launch_bounds__(256) void pc_sample_group_kernel(
       loc = wave_min_u64(loc);
       lastk = loc;
       int idx = (int)(uint32_t)loc;
-      if ((unsigned)idx >= (unsigned)P) idx = 0;  // unreachable for k <= P
+      if ((unsigned)idx >= (unsigned)Pv) idx = 0;  // unreachable for k <= P
+      if (RAGGED && r == 0) first = idx;
       if (lane == 0) nidx[((int64_t)cloud * n + ci) * k + r] = idx;
     }
+    if (RAGGED && lane < k - kk)  // the slots past the cloud repeat slot 0 (k <= 32 < 64 lanes)
+      nidx[((int64_t)cloud * n + ci) * k + kk + lane] = first;
   }
 }
 
@@ -598,11 +641,11 @@ size_t pc_bwd_lds_bytes(int C, int k, int F1, int F2, int D) {
 
 }  // namespace
 
-extern "C" int mmt_pc_sample_group(const float* points, int64_t ld_b, int64_t ld_s, int B, int S,
-                                   int P, int C, int n, int k, const int32_t* start,
-                                   const uint32_t* rng, int64_t sample_offset,
-                                   int32_t* centroid_idx, int32_t* neighbour_idx,
-                                   mmt_stream_t stream) {
+extern "C" int mmt_pc_sample_group_counts(const float* points, int64_t ld_b, int64_t ld_s, int B,
+                                          int S, int P, int C, int n, int k, const int32_t* start,
+                                          const uint32_t* rng, int64_t sample_offset,
+                                          const int32_t* counts, int32_t* centroid_idx,
+                                          int32_t* neighbour_idx, mmt_stream_t stream) {
   MMT_CHECK_ARG(points && centroid_idx && neighbour_idx, "mmt_pc_sample_group: null pointer");
   MMT_CHECK_ARG(B > 0 && S > 0 && (int64_t)B * S <= (1 << 24),
                 "mmt_pc_sample_group: B, S must be > 0 (B * S <= 2^24)");
@@ -615,16 +658,33 @@ extern "C" int mmt_pc_sample_group(const float* points, int64_t ld_b, int64_t ld
                 "mmt_pc_sample_group: strides (ld_s >= P * C, ld_b covers the S clouds)");
   const size_t lds = 64 + 1024 + 3 * sizeof(float) * (size_t)P;
   const dim3 grid(B * S);
-#define PC_SG(PPT)                                                                               \
-  hipLaunchKernelGGL(pc_sample_group_kernel<PPT>, grid, dim3(256), lds, as_stream(stream),       \
-                     points, ld_b, ld_s, S, P, C, n, k, start, rng, sample_offset, centroid_idx, \
-                     neighbour_idx, fault_word())
-  if (P <= 256) PC_SG(1);
-  else if (P <= 1024) PC_SG(4);
-  else PC_SG(16);
+  // without counts: the instantiation in which every count is the constant P (the kernel as it
+  // was before counts existed)
+#define PC_SG(PPT, RAGGED)                                                                        \
+  hipLaunchKernelGGL((pc_sample_group_kernel<PPT, RAGGED>), grid, dim3(256), lds,                 \
+                     as_stream(stream), points, ld_b, ld_s, S, P, C, n, k, start, rng,            \
+                     sample_offset, counts, centroid_idx, neighbour_idx, fault_word())
+  if (counts == nullptr) {
+    if (P <= 256) PC_SG(1, false);
+    else if (P <= 1024) PC_SG(4, false);
+    else PC_SG(16, false);
+  } else {
+    if (P <= 256) PC_SG(1, true);
+    else if (P <= 1024) PC_SG(4, true);
+    else PC_SG(16, true);
+  }
 #undef PC_SG
   MMT_CHECK_LAUNCH("mmt_pc_sample_group");
   return MMT_OK;
+}
+
+extern "C" int mmt_pc_sample_group(const float* points, int64_t ld_b, int64_t ld_s, int B, int S,
+                                   int P, int C, int n, int k, const int32_t* start,
+                                   const uint32_t* rng, int64_t sample_offset,
+                                   int32_t* centroid_idx, int32_t* neighbour_idx,
+                                   mmt_stream_t stream) {
+  return mmt_pc_sample_group_counts(points, ld_b, ld_s, B, S, P, C, n, k, start, rng, sample_offset,
+                                    nullptr, centroid_idx, neighbour_idx, stream);
 }
 
 #define PC_CHECK_EMBED(name, D)                                                                   \

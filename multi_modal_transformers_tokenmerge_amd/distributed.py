@@ -103,10 +103,13 @@ class DDPStep:
     # point_clouds: the clouds behind its PointCloud sets, a static device buffer likewise.
     # set_pad_mask, text_pad_mask: the observation pad masks (Octo.generate_readouts), static bool
     # device buffers likewise: a replay after the loader rewrote them gives the other masks' step.
+    # point_cloud_counts: the valid points of every cloud (Octo.generate_readouts), a static int32
+    # device buffer likewise: thin clouds become absent sets on the device, inside the graph.
 
     def __init__(self, model, state, txt, img, act, reducer: GradAllReducer | None = None,
                  stages="auto", use_graph: bool = True, txt_next=None, values=None,
-                 point_clouds=None, set_pad_mask=None, text_pad_mask=None):
+                 point_clouds=None, set_pad_mask=None, text_pad_mask=None,
+                 point_cloud_counts=None):
         self.model, self.state = model, state
         self.txt, self.img, self.act = txt, img, act
         if values is not None or model.n_values:    # ValueError now, not inside a capture
@@ -125,6 +128,13 @@ class DDPStep:
             self._vkw["set_pad_mask"] = set_pad_mask
         if text_pad_mask is not None:
             self._vkw["text_pad_mask"] = text_pad_mask
+        self.point_cloud_counts = point_cloud_counts
+        if point_cloud_counts is not None:    # ValueError now, not inside a capture
+            model._check_point_cloud_counts(point_cloud_counts, point_clouds, img.shape[0])
+            if not point_cloud_counts.is_contiguous():
+                raise ValueError("point_cloud_counts must be contiguous (a static buffer the "
+                                 "captured step reads in place)")
+            self._vkw["point_cloud_counts"] = point_cloud_counts
         self.t5_pf = (txt_next is not None and txt is not None
                       and getattr(model, "t5", None) is not None)
         self.txt_next = txt_next

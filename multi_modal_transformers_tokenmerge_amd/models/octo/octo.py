@@ -90,6 +90,7 @@ class Octo:
                                  f"give them {{0}}, got {{{ts.tokens_compressed_per_layer}}}")
         pc_sets = [ts for ts in sets0 if isinstance(ts, PointCloud)]
         self.n_pc_sets = len(pc_sets)
+        self.pc_set_ids = [i for i, ts in enumerate(sets0) if isinstance(ts, PointCloud)]
         self.pc_tokens = pc_sets[0].num_tokens if pc_sets else 0   # tokens per cloud
         for ts in pc_sets:
             if ts.tokens_compressed_per_layer:
@@ -342,6 +343,28 @@ class Octo:
             raise ValueError(f"fps_start must be an int32 {shape[:2]} tensor on the model's device")
         return point_clouds
 
+    def _check_point_cloud_counts(self, counts, point_clouds, B: int):
+        """The `point_cloud_counts` argument checked before any launch. ValueError: given without
+        point_clouds or to a model without PointCloud sets, not an int32 (B, n_pc_sets) tensor on
+        the model's device, or compression == "prune" (a thin cloud is an absent set, and the
+        pad masks cannot be combined with prune)."""
+        if counts is None:
+            return None
+        if not self.n_pc_sets:
+            raise ValueError("point_cloud_counts given, but input_sequence has no PointCloud set")
+        if point_clouds is None:
+            raise ValueError("point_cloud_counts given without point_clouds")
+        if self.cfg.compression == "prune":
+            raise ValueError('point_cloud_counts cannot be combined with compression == "prune": '
+                             "a thin cloud is an absent token set, and the attention's key_bias "
+                             "cannot be combined with wsum")
+        shape = (B, self.n_pc_sets)
+        if not torch.is_tensor(counts) or counts.dtype != torch.int32 or \
+                tuple(counts.shape) != shape or counts.device.type != self.device.type:
+            raise ValueError(f"point_cloud_counts must be an int32 {shape} tensor on the model's "
+                             f"device ({self.device.type})")
+        return counts.contiguous()
+
     def _check_pad_masks(self, set_pad_mask, text_pad_mask, B: int, images=None) -> bool:
         """The observation pad masks checked before any launch; returns whether one is given.
         ValueError: not a bool tensor on the model's device, set_pad_mask not (B, the set count
@@ -376,7 +399,8 @@ class Octo:
 
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
                           positions=None, tome=None, t5_out=None, values=None, point_clouds=None,
-                          fps_start=None, set_pad_mask=None, text_pad_mask=None):
+                          fps_start=None, set_pad_mask=None, text_pad_mask=None,
+                          point_cloud_counts=None):
         """Reference :91-126. Returns the final sequence (B, L_final, D) and the saved state.
         t5_out: the frozen T5 encoder's output for text_tokens, computed ahead (DDPStep's
         cross-step T5 pipeline); None runs the encoder here. values: the numbers behind the
@@ -393,12 +417,21 @@ class Octo:
         text set (an instruction's attention_mask). A masked token gets no attention weight as a
         key in any block, its row of the assembled sequence holds pos_embedding alone whatever
         the caller passed for it, and no gradient reaches a tokenizer through it (DESIGN.md,
-        "Observation pad masks"). Readout sets cannot be absent (reported by K.device_status())."""
+        "Observation pad masks"). Readout sets cannot be absent (reported by K.device_status()).
+        point_cloud_counts: int32 (B, n_pc_sets) on the device, the leading rows of every cloud of
+        point_clouds that are points (tokenizers/pointclouds/depth.py gives both); the other rows
+        are never read. A cloud with fewer points than its set has tokens is an absent set for
+        its sample, as if set_pad_mask flagged it; the counts are read on the device, so a
+        replayed step follows new contents of the buffer. Refused without point_clouds, without
+        PointCloud sets and with compression == "prune" ("Ragged clouds and depth
+        back-projection")."""
         B = images.shape[0]
         D = self.D
         values = self._check_values(values, B)
+        counts = self._check_point_cloud_counts(point_cloud_counts, point_clouds, B)
         point_clouds = self._check_point_clouds(point_clouds, B, fps_start)
         padded = self._check_pad_masks(set_pad_mask, text_pad_mask, B, images)
+        padded = padded or counts is not None
         st: Dict = dict(B=B, train=train, rng=rng, sample_offset=sample_offset)
         txt, T = None, max(self.n_text, 1)
         if self.has_text:
@@ -412,10 +445,17 @@ class Octo:
                 txt = t5_out
         pad = None
         if padded:
-            words = (None if set_pad_mask is None
-                     else K.pad_mask_pack(set_pad_mask, self.readout_set_bits))
+            if counts is not None:
+                # a cloud with fewer points than tokens is an absent set of its sample: a bit of
+                # the packed words, from the counts on the device (no host synchronisation)
+                words = K.pad_mask_pack_counts(set_pad_mask, self.n_sets, self.readout_set_bits,
+                                               counts, self.pc_set_ids,
+                                               [self.pc_tokens] * self.n_pc_sets)
+            else:
+                words = (None if set_pad_mask is None
+                         else K.pad_mask_pack(set_pad_mask, self.readout_set_bits))
             pad = st["pad"] = (words, text_pad_mask)
-            if words is not None and self.image_sets:
+            if set_pad_mask is not None and self.image_sets:   # counts make no camera absent
                 # the stem's GroupNorm runs over all patches of all cameras of a sample: it reads
                 # a copy of the images with the absent cameras' pixels zeroed, so they reach no
                 # present camera's tokens through its statistics
@@ -437,7 +477,7 @@ class Octo:
         if point_clouds is not None:  # the rows of kind 4
             st["pc_sv"] = self.point_cloud_tokenizer.forward(
                 point_clouds, self.pc_tokens, self.pc_rows, self.pos_embed.data, x0, train, rng,
-                sample_offset, fps_start)
+                sample_offset, fps_start, counts)
         if padded:
             # after every tokenizer has written x0: the masked rows hold pos_embedding alone
             K.pad_mask_rows_fwd(x0, self.pos_embed.data, self.layer_sets[0][1], words,
@@ -477,7 +517,8 @@ class Octo:
     def compute_diffusion_denoise_loss(self, text_tokens, images, actions, train=True, rng=None,
                                        sample_offset=0, inject: Optional[dict] = None, t5_out=None,
                                        action_pad_mask=None, values=None, point_clouds=None,
-                                       set_pad_mask=None, text_pad_mask=None):
+                                       set_pad_mask=None, text_pad_mask=None,
+                                       point_cloud_counts=None):
         """Reference :139-145. Returns (loss (1,) fp32 device tensor, saved state). inject (tests):
         positions (rt, ct), t, eps, tome (per block an (unm, src, dst) triple of int32 device
         tensors or None) replace the step's own draws / matching. t5_out: the frozen encoder's
@@ -502,6 +543,7 @@ class Octo:
                                         inject.get("positions"), inject.get("tome"), t5_out,
                                         values=values, point_clouds=point_clouds,
                                         set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                        point_cloud_counts=point_cloud_counts,
                                         fps_start=inject.get("fps_start"))
         B = xL.shape[0]
         if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
@@ -539,18 +581,20 @@ class Octo:
     def predict_diffusion_denoise_term(self, text_tokens, images, time, noisy_actions, rng=None,
                                        sample_offset=0, train=True, values=None,
                                        point_clouds=None,
-                                       set_pad_mask=None, text_pad_mask=None):
+                                       set_pad_mask=None, text_pad_mask=None,
+                                       point_cloud_counts=None):
         """Reference :130-137: readouts -> pooled readouts (their mean, or the attention
         pooling) -> OctoDenoise (diffusion.py:88-107)."""
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                        values=values, point_clouds=point_clouds,
-                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                       point_cloud_counts=point_cloud_counts)
         return self.head.predict_denoise_term_mean(self._readout_pooled(xL), time, noisy_actions)
 
     def predict_diffusion_action(self, text_tokens, images, rng, sample_offset=0, train=True,
                                  z: Optional[torch.Tensor] = None, return_noise=False,
                                  positions=None, sampler=None, values=None, point_clouds=None,
-                                 set_pad_mask=None, text_pad_mask=None,
+                                 set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None,
                                  fps_start=None):
         """Reference :147-154: readouts (the reference's backbone always runs with
         train=True, :120, and its image encoder samples positions by default) -> readout mean ->
@@ -561,6 +605,7 @@ class Octo:
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset, positions,
                                        values=values, point_clouds=point_clouds,
                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                       point_cloud_counts=point_cloud_counts,
                                        fps_start=fps_start)
         if self.pooling is not None:
             e = self._readout_pooled(xL)
@@ -612,12 +657,13 @@ class Octo:
 
     def predict_continuous_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
                                   values=None, point_clouds=None,
-                                  set_pad_mask=None, text_pad_mask=None):
+                                  set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
         """Reference :158-165 -> (B, pred_horizon, A) fp32 ((B, 1, A) as the reference)."""
         h = self._need(self.continuous_head, "continuous")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                        values=values, point_clouds=point_clouds,
-                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                       point_cloud_counts=point_cloud_counts)
         return h.forward(self._readout_mean(xL))
 
     @staticmethod
@@ -627,7 +673,7 @@ class Octo:
 
     def compute_l2_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
                         action_pad_mask=None, values=None, point_clouds=None,
-                        set_pad_mask=None, text_pad_mask=None):
+                        set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
         """Reference :167-174, batch-averaged as continuous_train_step (:262). (loss, saved).
         actions (B, pred_horizon, A) or flat; OctoConfig.continuous_loss picks the squared error
         or L1. action_pad_mask: bool, the actions' shape, True where a component is real: padded
@@ -637,26 +683,28 @@ class Octo:
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         values=values, point_clouds=point_clouds,
-                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                        point_cloud_counts=point_cloud_counts)
         loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
 
     def predict_action_logits(self, text_tokens, images, rng=None, sample_offset=0, train=True,
                               values=None, point_clouds=None,
-                              set_pad_mask=None, text_pad_mask=None):
+                              set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
         """Reference :178-185 -> (B, A, num_bins) fp32, (B, pred_horizon, A, num_bins) with a
         pred_horizon > 1."""
         h = self._need(self.categorical_head, "categorical")
         xL, _ = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                        values=values, point_clouds=point_clouds,
-                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                       set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                       point_cloud_counts=point_cloud_counts)
         return h.forward(self._readout_group_means(xL))
 
     def predict_categorical_action(self, text_tokens, images, rng=None, sample_offset=0, train=True,
                                    mode="argmax", temperature=1.0, values=None,
                                    point_clouds=None,
-                                   set_pad_mask=None, text_pad_mask=None):
+                                   set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
         """The categorical head rolled out: logits (predict_action_logits) decoded to actions
         (B, pred_horizon, A) fp32 through bin_values, by argmax or (mode "sample") one draw per
         component from softmax(logits / temperature) keyed by rng and sample_offset
@@ -664,12 +712,13 @@ class Octo:
         h = self._need(self.categorical_head, "categorical")
         logits = self.predict_action_logits(text_tokens, images, rng, sample_offset, train,
                                             values=values, point_clouds=point_clouds,
-                                            set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                            set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                            point_cloud_counts=point_cloud_counts)
         return h.decode(logits, rng, sample_offset, mode, temperature)[0]
 
     def compute_ce_loss(self, text_tokens, images, actions, train=True, rng=None, sample_offset=0,
                         action_pad_mask=None, values=None, point_clouds=None,
-                        set_pad_mask=None, text_pad_mask=None):
+                        set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
         """Reference :187-198, averaged as categorical_train_step (:302). (loss, saved).
         actions (B, pred_horizon, A) or flat. action_pad_mask: compute_l2_loss's; the loss is the
         mean of the cross entropy over the real components."""
@@ -677,7 +726,8 @@ class Octo:
         self._check_pad_mask(action_pad_mask)
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         values=values, point_clouds=point_clouds,
-                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask)
+                                        set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
+                                        point_cloud_counts=point_cloud_counts)
         loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
@@ -1276,7 +1326,7 @@ def _train_step(loss_fn, model: Octo, train_state: OCTOTrainState, text_tokens, 
 
 
 def _step_kw(action_pad_mask, values, point_clouds=None, set_pad_mask=None,
-             text_pad_mask=None) -> dict:
+             text_pad_mask=None, point_cloud_counts=None) -> dict:
     """The optional keywords of a loss, passed only when given."""
     kw = {} if action_pad_mask is None else {"action_pad_mask": action_pad_mask}
     if values is not None:
@@ -1287,39 +1337,45 @@ def _step_kw(action_pad_mask, values, point_clouds=None, set_pad_mask=None,
         kw["set_pad_mask"] = set_pad_mask
     if text_pad_mask is not None:
         kw["text_pad_mask"] = text_pad_mask
+    if point_cloud_counts is not None:
+        kw["point_cloud_counts"] = point_cloud_counts
     return kw
 
 
 def continuous_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
                           action_pad_mask=None, values=None, point_clouds=None,
-                          set_pad_mask=None, text_pad_mask=None):
+                          set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
     """Reference octo.py:242-280: value_and_grad of mean(compute_l2_loss), apply_gradients,
     metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_l2_loss's;
-    set_pad_mask, text_pad_mask: generate_readouts'."""
-    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
+    set_pad_mask, text_pad_mask, point_cloud_counts: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask,
+                  point_cloud_counts)
     return _train_step(model.compute_l2_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def categorical_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
                            action_pad_mask=None, values=None, point_clouds=None,
-                           set_pad_mask=None, text_pad_mask=None):
+                           set_pad_mask=None, text_pad_mask=None, point_cloud_counts=None):
     """Reference octo.py:282-320: value_and_grad of mean(compute_ce_loss), apply_gradients,
     metrics merge. Returns (train_state, grads). action_pad_mask, values: compute_ce_loss's;
-    set_pad_mask, text_pad_mask: generate_readouts'."""
-    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
+    set_pad_mask, text_pad_mask, point_cloud_counts: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask,
+                  point_cloud_counts)
     return _train_step(model.compute_ce_loss, model, train_state, text_tokens, images, actions,
                        **kw)
 
 
 def diffusion_train_step(model: Octo, train_state: OCTOTrainState, text_tokens, images, actions,
                          inject: Optional[dict] = None, action_pad_mask=None, values=None,
-                         point_clouds=None, set_pad_mask=None, text_pad_mask=None):
+                         point_clouds=None, set_pad_mask=None, text_pad_mask=None,
+                         point_cloud_counts=None):
     """Reference octo.py:204-240: value_and_grad of the denoise loss, apply_gradients, metrics
     merge. Returns (train_state, grads) like the reference; grads are views of the flat gradient
     buffer by parameter name, the loss is train_state.last_loss (device) and the running average
     train_state.metrics. action_pad_mask, values: compute_diffusion_denoise_loss's;
-    set_pad_mask, text_pad_mask: generate_readouts'."""
-    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask)
+    set_pad_mask, text_pad_mask, point_cloud_counts: generate_readouts'."""
+    kw = _step_kw(action_pad_mask, values, point_clouds, set_pad_mask, text_pad_mask,
+                  point_cloud_counts)
     return _train_step(model.compute_diffusion_denoise_loss, model, train_state, text_tokens,
                        images, actions, inject=inject, **kw)

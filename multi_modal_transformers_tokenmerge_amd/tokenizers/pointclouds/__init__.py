@@ -1,0 +1,1 @@
+from .depth import depth_to_point_cloud  # noqa: F401

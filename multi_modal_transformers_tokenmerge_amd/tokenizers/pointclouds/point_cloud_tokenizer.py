@@ -14,8 +14,9 @@ where the reference cannot be followed (DESIGN.md §3 "Point-cloud tokens"). All
 The three departures from the reference: no BatchNorm (its ``use_running_average=is_training`` is
 inverted and batch statistics would couple samples), a max over the neighbour axis as in the PCT
 paper (the reference never reduces it), and ``output_dense`` (F2 -> D), which the reference lacks.
-The kernels are csrc/pointcloud.hip (mmt_pc_sample_group, mmt_pc_embed_fwd / _bwd,
-include/mmt_api.h); no gradient reaches the points.
+The kernels are csrc/pointcloud.hip (mmt_pc_sample_group, mmt_pc_sample_group_counts for ragged
+clouds, mmt_pc_embed_fwd / _bwd, include/mmt_api.h); no gradient reaches the points. depth.py turns
+depth images into clouds with counts.
 """
 from __future__ import annotations
 
@@ -81,17 +82,19 @@ class PointCloudTokenizer(Bindable):
     # ------------------------------------------------------------------ the hooks Octo uses
     def forward(self, points: torch.Tensor, n: int, rows: torch.Tensor, pe: torch.Tensor,
                 x0: torch.Tensor, train: bool = False, rng=None, sample_offset: int = 0,
-                fps_start=None) -> dict:
+                fps_start=None, counts=None) -> dict:
         """points (B, S, P, C) fp32, rows (S n,) int32: samples and groups every cloud, writes
         x0[b, rows[s n + m]] = token(b, s, m) + pe[rows[s n + m]] (no other row of x0) and returns
         the backward's saved state. The first centroid: fps_start (B, S) int32 if given, the
-        counter-RNG draw in train mode, point 0 in eval mode."""
+        counter-RNG draw in train mode, point 0 in eval mode. counts (B, S) int32: ragged clouds,
+        the leading counts[b, s] rows of a cloud are its points (K.pc_sample_group); the
+        embedding kernels take the padded groups as they are."""
         if points.shape[-1] != self.C:
             raise ValueError(f"points have {points.shape[-1]} features, the tokenizer "
                              f"point_features = {self.C}")
         cidx, nidx = K.pc_sample_group(points, n, self.k, fps_start,
                                        rng if (train and fps_start is None) else None,
-                                       sample_offset)
+                                       sample_offset, counts)
         w = [p.data for p in self._all()]
         argmax = K.pc_embed_fwd(points, cidx, nidx, *w, pe, rows, x0)
         return dict(points=points, cidx=cidx, nidx=nidx, argmax=argmax)
@@ -110,23 +113,39 @@ class PointCloudTokenizer(Bindable):
             raise ValueError("points must be an fp32 device tensor (..., P, C)")
         return points.reshape(-1, 1, *points.shape[-2:]).contiguous()
 
-    def sample_and_group(self, points: torch.Tensor, n: int, start=None):
+    def _counts(self, counts, p4: torch.Tensor):
+        """counts: None, an int, or an int32 tensor (...) -> None or int32 (clouds, 1)."""
+        if counts is None:
+            return None
+        if not torch.is_tensor(counts):
+            return torch.full((p4.shape[0], 1), int(counts), dtype=torch.int32, device=p4.device)
+        if counts.dtype != torch.int32 or counts.numel() != p4.shape[0] or \
+                counts.device != p4.device:
+            raise ValueError("counts must be an int32 tensor on the points' device with one "
+                             f"entry per cloud ({p4.shape[0]})")
+        return counts.reshape(p4.shape[0], 1).contiguous()
+
+    def sample_and_group(self, points: torch.Tensor, n: int, start=None, counts=None):
         """points (..., P, C) -> (centroid_idx (..., n), neighbour_idx (..., n, k)) int32.
-        start: None (point 0), an int, or an int32 tensor (...) of first centroids."""
+        start: None (point 0), an int, or an int32 tensor (...) of first centroids. counts: None
+        (every cloud has P points), an int, or an int32 tensor (...): the leading rows of each
+        cloud that are points."""
         p4 = self._clouds(points)
         lead = points.shape[:-2]
+        counts = self._counts(counts, p4)
         if start is not None:
             if not torch.is_tensor(start):
                 start = torch.full((p4.shape[0], 1), int(start), dtype=torch.int32,
                                    device=points.device)
             start = start.to(torch.int32).reshape(p4.shape[0], 1).contiguous()
-        cidx, nidx = K.pc_sample_group(p4, n, self.k, start)
+        cidx, nidx = K.pc_sample_group(p4, n, self.k, start, counts=counts)
         return cidx.view(*lead, n), nidx.view(*lead, n, self.k)
 
-    def farthest_point_sampling(self, points: torch.Tensor, num_samples: int, start=None):
+    def farthest_point_sampling(self, points: torch.Tensor, num_samples: int, start=None,
+                                counts=None):
         """Reference :42-92 on the device: the (..., num_samples) int32 indices of the sampled
-        points."""
-        return self.sample_and_group(points, num_samples, start)[0]
+        points. counts: sample_and_group's."""
+        return self.sample_and_group(points, num_samples, start, counts)[0]
 
     def knn(self, points: torch.Tensor, centroid: int, k: int | None = None):
         """Reference :106-116 on the device: the k nearest points of point ``centroid`` of one
@@ -135,9 +154,11 @@ class PointCloudTokenizer(Bindable):
         tok = self if k is None or k == self.k else PointCloudTokenizer(k, self.C, (self.F1, self.F2))
         return tok.sample_and_group(points, 1, int(centroid))[1].reshape(-1, tok.k)[0]
 
-    def __call__(self, points: torch.Tensor, n: int, start=None) -> torch.Tensor:
-        """(..., P, C) fp32 -> (..., n, D) fp32: the tokens alone, no position term."""
+    def __call__(self, points: torch.Tensor, n: int, start=None, counts=None) -> torch.Tensor:
+        """(..., P, C) fp32 -> (..., n, D) fp32: the tokens alone, no position term. counts:
+        sample_and_group's (a cloud with fewer points than n repeats its tokens)."""
         p4 = self._clouds(points)
+        counts = self._counts(counts, p4)
         if self.w1 is None and self.D is None:
             raise ValueError("an unbound PointCloudTokenizer needs embedding_dim")
         self._ensure(points.device, self.D)
@@ -147,5 +168,5 @@ class PointCloudTokenizer(Bindable):
         out = torch.empty((B, n, self.D), dtype=torch.float32, device=dev)
         rows = torch.arange(n, dtype=torch.int32, device=dev)
         zero = torch.zeros((n, self.D), dtype=torch.float32, device=dev)  # no position term
-        self.last_saved = self.forward(p4, n, rows, zero, out, fps_start=start)
+        self.last_saved = self.forward(p4, n, rows, zero, out, fps_start=start, counts=counts)
         return out.view(*points.shape[:-2], n, self.D)
