@@ -978,6 +978,59 @@ int mmt_depth_unproject(const void* depth, int depth_is_f32, int B, int S, int H
                         float depth_scale, float z_min, float z_max, int P, float* points,
                         int32_t* counts, mmt_stream_t stream);
 
+/* ------------------------------------------------------------------ image augmentation
+ * Random resized crop plus brightness, contrast and saturation jitter of uint8 camera frames on
+ * the device (csrc/augment.hip): the Octo training recipe (primary camera: crop + colour; wrist
+ * camera: colour alone), keyed like every other random stream by (seed, step, global sample).
+ * images, out: uint8 (B, I, H, W, 3) contiguous, 16-B aligned, not overlapping; rng: the two-word
+ * RNG state {seed, step}; image_camera: int32 (I,) on the device, the camera of each image slot;
+ * cam_params: fp32 (n_cam, 9) on the device = scale_lo, scale_hi, ratio_lo, ratio_hi, brightness,
+ * contrast_lo, contrast_hi, sat_lo, sat_hi per camera; params_out (optional): fp32 (B, n_cam, 8) =
+ * w, h, x0, y0, d, fc, fs, 0 of every (sample, camera), for callers that move other labels with
+ * the crop. Every float operation below is individually rounded to fp32 (no FMA), so numpy
+ * float32 restates the pixels bit for bit.
+ *   draws    one set per (global sample g = sample_offset + b, camera c), shared by every image
+ *            slot of the sample with that camera (a history window is cropped and tinted alike):
+ *            key = stream_key(seed, step, 0xFFF6, c), u_j = (draw_u32(key, (8 g + j) mod 2^32)
+ *            >> 8) / 2^24 for j = 0 .. 6. Layer word 0xFFF6 is this entry's alone: 0xFFF7 is the
+ *            point-cloud start's, 0xFFF8 the categorical decode's, 0xFFF9 .. 0xFFFF are taken
+ *            (see mmt_diffusion_loss_multi).
+ *   params   area = scale_lo + u0 (scale_hi - scale_lo), rho = ratio_lo + u1 (ratio_hi - ratio_lo)
+ *            (uniform, not log-uniform), w = min(1, sqrt(area rho)), h = min(1, sqrt(area / rho)),
+ *            x0 = u2 (1 - w), y0 = u3 (1 - h), d = ((2 u4 - 1) brightness) 255,
+ *            fc = contrast_lo + u5 (contrast_hi - contrast_lo), fs = sat_lo + u6 (sat_hi - sat_lo)
+ *   resample bilinear, corner-aligned (crop_and_resize): output row r samples sy = y0 (H - 1) +
+ *            float(r) h, iy = min(floor(sy), H - 1), iy1 = min(iy + 1, H - 1), ty = sy - float(iy);
+ *            columns likewise with x0, w, W. Per channel top = p00 + (p01 - p00) tx, bot = p10 +
+ *            (p11 - p10) tx, v = top + (bot - top) ty.
+ *   mean     per channel over the integer source box the crop reads, rows iy(0) .. iy1(H - 1),
+ *            columns ix(0) .. ix1(W - 1): m = float(sum) / float(n), sum the exact integer sum of
+ *            the bytes, n the box area, both conversions to nearest. No float enters the sum: no
+ *            summation order can show in the result.
+ *   colour   v1 = v + d, mb = m + d, v2 = (v1 - mb) fc + mb, gray = (0.299 r2 + 0.587 g2) +
+ *            0.114 b2, v3 = gray + (v2 - gray) fs, out = uint8(rint(min(max(v3, 0), 255))), rint to
+ *            even. One clamp, at the end.
+ * workspace: >= mmt_image_augment_workspace(B, I) bytes, 16-B aligned (the integer partial sums,
+ * MMT_AUGMENT_SPLIT per image; every word read is written by the call first). Two launches,
+ * stream-ordered, graph-capturable, no allocation, no atomics. MMT_ERR_INVALID before a launch: a
+ * null pointer (params_out may be), images / out / workspace not 16-B aligned or another pointer
+ * not 4-B aligned, B, I, H or W < 1, H or W > MMT_AUGMENT_MAX_SIDE, I > MMT_AUGMENT_MAX_IMAGES,
+ * B I > MMT_AUGMENT_MAX_FRAMES, n_cam outside 1 .. MMT_AUGMENT_MAX_CAMERAS, sample_offset < 0,
+ * out overlapping images, a workspace too small. image_camera and cam_params are device data: an
+ * entry of image_camera outside [0, n_cam) is read as 0 (MMT_FAULT_ROW_INDEX), and with ranges
+ * that are not ordered, positive and finite the pixels are unspecified, every read and write
+ * still inside the tensors (every sample index is clamped into its image). */
+#define MMT_AUGMENT_MAX_SIDE 2048
+#define MMT_AUGMENT_MAX_IMAGES 64
+#define MMT_AUGMENT_MAX_CAMERAS 16
+#define MMT_AUGMENT_MAX_FRAMES (1 << 24)
+#define MMT_AUGMENT_SPLIT 8
+int64_t mmt_image_augment_workspace(int B, int I);
+int mmt_image_augment(const uint8_t* images, int B, int I, int H, int W, const uint32_t* rng,
+                      int64_t sample_offset, const int32_t* image_camera, const float* cam_params,
+                      int n_cam, uint8_t* out, float* params_out, void* workspace,
+                      int64_t workspace_bytes, mmt_stream_t stream);
+
 /* ------------------------------------------------------------------ QK-norm
  * flax.linen.SelfAttention(normalize_qk=True): LayerNorm(use_bias=False) over the head dimension of
  * the projected queries and keys before the dot product (`query_ln`, `key_ln`; the reference's
@@ -1157,6 +1210,9 @@ int mmt_sampler_last_route(void);
  * g = sample_offset + b; eps: site 2 at counter g A + j), so K = 1 reproduces its draws bit for
  * bit. Draw k >= 1 uses layer word 0xFFF9 (no other stream does: 0xFFFA .. 0xFFFE are the head's
  * and the sampler's, 0xFFFF the stem's), site 2 k for t and 2 k + 1 for eps, same counters.
+ * The layer words taken, for whoever picks the next: 0xFFF6 mmt_image_augment, 0xFFF7 the
+ * point-cloud start (mmt_pc_sample_group), 0xFFF8 mmt_head_categorical_decode, 0xFFF9 this entry,
+ * 0xFFFA .. 0xFFFF as above; 0xFFF5 is the next free one.
  * Supported: A % 8 == 0, 8 <= A <= 64; H % 8 == 0, H <= 1024; 1 <= K <= 64; steps >= 1;
  * ld_w1 % 8 == 0, w1 and w2 16-B aligned; rng or both injections. Anything else is
  * MMT_ERR_INVALID before a launch. Graph-capturable, allocates nothing, no float atomics: a wave
@@ -1262,7 +1318,8 @@ int mmt_head_categorical(const float* z, int64_t ldz, int R, int N, const float*
  * mode MMT_DECODE_ARGMAX: the largest logit, the first index on ties.
  * mode MMT_DECODE_SAMPLE: one draw per row from softmax(z / temperature), temperature > 0, by
  * inverse CDF: key stream_key(seed, step, 0xFFF8, 1) of rng = {seed, step} (layer word 0xFFF8 is
- * this entry's alone: 0xFFF9 .. 0xFFFF are taken, see mmt_diffusion_loss_multi), counter
+ * this entry's alone: 0xFFF6, 0xFFF7 and 0xFFF9 .. 0xFFFF are taken, see
+ * mmt_diffusion_loss_multi), counter
  * (sample_offset + b) G + g for row r = b G + g (G = h A groups per sample, R % G == 0);
  * u = ((draw_u32 >> 8) + 0.5) / 2^24 in fp32 (the sum is exact below 2^23 and rounds to even
  * above, so u lies in (0, 1]; oracle/rng.py restates the draw bit for bit); the class is the

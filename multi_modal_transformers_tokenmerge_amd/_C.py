@@ -97,6 +97,8 @@ SIGNATURES: dict[str, list] = {
     "mmt_pc_sample_group": [P, L, L, I, I, I, I, I, I, P, P, L, P, P, P],
     "mmt_pc_sample_group_counts": [P, L, L, I, I, I, I, I, I, P, P, L, P, P, P, P],
     "mmt_depth_unproject": [P, I, I, I, I, I, P, P, P, F, F, F, I, P, P, P],
+    "mmt_image_augment_workspace": [I, I],
+    "mmt_image_augment": [P, I, I, I, I, P, L, P, P, I, P, P, P, L, P],
     "mmt_pc_embed_fwd": [P, L, L, I, I, I, I, I, I, P, P, I, I, P, P, P, P, P, P, P, P, I, P, L, L, P,
                          P],
     "mmt_pc_embed_bwd_workspace": [I, I, I, I, I, I, I],
@@ -152,6 +154,7 @@ _VOID = {"mmt_tome_set_match_path", "mmt_gemm_set_variant"}
 _RESTYPE = {"mmt_workspace_size": L,      # returns a byte count (negative: error)
             "mmt_pc_embed_bwd_workspace": L,  # returns a byte count (negative: error)
             "mmt_qk_norm_bwd_workspace": L,   # returns a byte count (negative: error)
+            "mmt_image_augment_workspace": L,  # returns a byte count (negative: error)
             "mmt_gemm_colsum_rows": I,    # returns a row count
             "mmt_gemm_last_route": I,     # returns a ROUTE_* value
             "mmt_attn_last_route": I,     # returns an ATTN_ROUTE_* value
@@ -362,6 +365,9 @@ PC_MAX_POINTS, PC_MAX_TOKENS, PC_MAX_NEIGHBOURS = 4096, 256, 32
 PC_MIN_FEATURES, PC_MAX_FEATURES, PC_MAX_WIDTH = 3, 8, 4096
 PC_HIDDEN_WIDTHS = (32, 64, 128)
 DEPTH_MAX_PIXELS = 1 << 20           # mmt_depth_unproject: H * W at most
+# MMT_AUGMENT_* limits of mmt_image_augment: the side of a frame, the image slots of a sample, the
+# cameras, B * I
+AUGMENT_MAX_SIDE, AUGMENT_MAX_IMAGES, AUGMENT_MAX_CAMERAS, AUGMENT_MAX_FRAMES = 2048, 64, 16, 1 << 24
 QK_NORM_WIDTHS = (32, 64, 128, 256)   # head widths of mmt_qk_norm_fwd / _bwd
 HEAD_LOSS_MSE, HEAD_LOSS_L1 = 0, 1   # MMT_HEAD_LOSS_* (mmt_head_continuous loss_kind)
 DECODE_ARGMAX, DECODE_SAMPLE = 0, 1  # MMT_DECODE_* (mmt_head_categorical_decode mode)

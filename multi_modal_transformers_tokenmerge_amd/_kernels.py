@@ -1464,6 +1464,135 @@ def depth_unproject(depth: torch.Tensor, intrinsics: torch.Tensor, num_points: i
     return out, counts
 
 
+AUGMENT_FIELDS = ("scale_lo", "scale_hi", "ratio_lo", "ratio_hi", "brightness", "contrast_lo",
+                  "contrast_hi", "sat_lo", "sat_hi")   # a row of mmt_image_augment's cam_params
+
+
+def check_augment_tables(image_camera, cam_params, n_images: int | None = None):
+    """The host values behind mmt_image_augment's two device tables, checked: image_camera, one
+    camera index per image slot, and cam_params, one row of AUGMENT_FIELDS per camera. Returns
+    (list of ints, list of 9-tuples of floats). ValueError: no or more than 64 image slots (or not
+    n_images of them), no or more than 16 cameras, a row that is not 9 finite numbers, a camera
+    index outside 0 .. n_cam - 1 or no integer, lo > hi in a range, scale_lo <= 0, scale_hi > 1,
+    ratio_lo <= 0, brightness outside [0, 1], a negative contrast or saturation bound."""
+    import math
+    try:
+        rows = [tuple(float(v) for v in row) for row in cam_params]
+        cams = list(image_camera)
+    except (TypeError, ValueError):
+        raise ValueError("image_camera must be a sequence of camera indices and cam_params a "
+                         f"sequence of rows {AUGMENT_FIELDS}") from None
+    n_cam = len(rows)
+    if not 1 <= n_cam <= _C.AUGMENT_MAX_CAMERAS:
+        raise ValueError(f"cam_params holds {n_cam} cameras, need 1 .. {_C.AUGMENT_MAX_CAMERAS}")
+    if not 1 <= len(cams) <= _C.AUGMENT_MAX_IMAGES or (n_images is not None
+                                                        and len(cams) != n_images):
+        want = f"{n_images}" if n_images is not None else f"1 .. {_C.AUGMENT_MAX_IMAGES}"
+        raise ValueError(f"image_camera names {len(cams)} image slots, need {want}")
+    for c in cams:
+        if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < n_cam:
+            raise ValueError(f"image_camera entry {c!r} is no camera index in 0 .. {n_cam - 1}")
+    for i, row in enumerate(rows):
+        if len(row) != 9 or not all(math.isfinite(v) for v in row):
+            raise ValueError(f"camera {i}: need 9 finite numbers {AUGMENT_FIELDS}, got {row}")
+        slo, shi, rlo, rhi, br, clo, chi, tlo, thi = row
+        if slo > shi or rlo > rhi or clo > chi or tlo > thi:
+            raise ValueError(f"camera {i}: a range has lo > hi: {row}")
+        if not 0.0 < slo or shi > 1.0:
+            raise ValueError(f"camera {i}: need 0 < scale_lo <= scale_hi <= 1, got ({slo}, {shi})")
+        if not 0.0 < rlo:
+            raise ValueError(f"camera {i}: need ratio_lo > 0, got {rlo}")
+        if not 0.0 <= br <= 1.0:
+            raise ValueError(f"camera {i}: brightness {br} outside [0, 1]")
+        if clo < 0.0 or tlo < 0.0:
+            raise ValueError(f"camera {i}: contrast and saturation bounds must be >= 0, got "
+                             f"({clo}, {chi}), ({tlo}, {thi})")
+    return [int(c) for c in cams], rows
+
+
+def image_augment_workspace(B: int, I: int) -> int:
+    """Bytes of mmt_image_augment's workspace for B samples of I image slots."""
+    return _C.call("mmt_image_augment_workspace", int(B), int(I))
+
+
+def image_augment(images: torch.Tensor, rng: torch.Tensor, image_camera: torch.Tensor,
+                  cam_params: torch.Tensor, sample_offset: int = 0,
+                  out: torch.Tensor | None = None, params_out: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None, tables=None) -> torch.Tensor:
+    """uint8 camera frames (B, I, H, W, 3), contiguous -> their augmented copy (mmt_image_augment,
+    include/mmt_api.h "image augmentation"): a random resized crop resampled bilinearly to (H, W)
+    plus brightness, contrast and saturation jitter, one draw per (global sample sample_offset + b,
+    camera) from rng = the int32 {seed, step} words on the device. image_camera: int32 (I,) on the
+    device, the camera of each image slot; cam_params: fp32 (n_cam, 9) on the device, a row of
+    AUGMENT_FIELDS per camera. params_out (optional): fp32 (B, n_cam, 8), receives w, h, x0, y0,
+    d, fc, fs, 0. workspace (optional): a uint8 buffer of image_augment_workspace(B, I) bytes;
+    allocated when missing. tables: the host values of (image_camera, cam_params) as
+    check_augment_tables returned them; None reads the two tensors back (a synchronisation: pass
+    tables inside a graph capture). ValueError before any launch: a dtype, device, contiguity or
+    shape fault, H or W above 2048, I above 64, out overlapping images, and
+    check_augment_tables' faults."""
+    for t, what in ((images, "images"), (rng, "rng"), (image_camera, "image_camera"),
+                    (cam_params, "cam_params")):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what} must be a tensor")
+    if images.dtype != torch.uint8 or images.dim() != 5 or images.shape[-1] != 3:
+        raise ValueError(f"images must be uint8 (B, I, H, W, 3), got {images.dtype} "
+                         f"{tuple(images.shape)}")
+    if not images.is_cuda:
+        raise ValueError("images must live on the GPU")
+    dev = images.device
+    for t, what in ((rng, "rng"), (image_camera, "image_camera"), (cam_params, "cam_params"),
+                    (out, "out"), (params_out, "params_out"), (workspace, "workspace")):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{what} must live on the images' device")
+    B, I, H, W, _ = images.shape
+    if B < 1 or not 1 <= I <= _C.AUGMENT_MAX_IMAGES or B * I > _C.AUGMENT_MAX_FRAMES or \
+            not 1 <= H <= _C.AUGMENT_MAX_SIDE or not 1 <= W <= _C.AUGMENT_MAX_SIDE:
+        raise ValueError(f"images {tuple(images.shape)}: need B >= 1, 1 <= I <= "
+                         f"{_C.AUGMENT_MAX_IMAGES}, 1 <= H, W <= {_C.AUGMENT_MAX_SIDE}")
+    if not images.is_contiguous() or images.data_ptr() % 16:
+        raise ValueError("images must be contiguous and 16-B aligned")
+    if rng.dtype != torch.int32 or rng.numel() != 2 or not rng.is_contiguous():
+        raise ValueError("rng must be the contiguous int32 {seed, step} pair")
+    _check_i32(image_camera, (I,), "image_camera")
+    if cam_params.dtype != torch.float32 or cam_params.dim() != 2 or cam_params.shape[1] != 9 or \
+            not cam_params.is_contiguous():
+        raise ValueError("cam_params must be contiguous fp32 (n_cam, 9)")
+    n_cam = cam_params.shape[0]
+    if tables is None:
+        tables = check_augment_tables(image_camera.tolist(), cam_params.tolist(), I)
+    elif len(tables[0]) != I or len(tables[1]) != n_cam:
+        raise ValueError(f"tables describe {len(tables[0])} image slots and {len(tables[1])} "
+                         f"cameras, the tensors {I} and {n_cam}")
+    if isinstance(sample_offset, bool) or int(sample_offset) != sample_offset or sample_offset < 0:
+        raise ValueError(f"sample_offset must be an integer >= 0, got {sample_offset!r}")
+    if out is None:
+        out = torch.empty_like(images)
+    else:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.shape != images.shape or \
+                not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be a contiguous 16-B aligned uint8 tensor of the images' "
+                             "shape")
+        n = images.numel()
+        if out.data_ptr() < images.data_ptr() + n and images.data_ptr() < out.data_ptr() + n:
+            raise ValueError("out must not overlap images (the crop gathers: no in-place form)")
+    if params_out is not None and (params_out.dtype != torch.float32
+                                   or tuple(params_out.shape) != (B, n_cam, 8)
+                                   or not params_out.is_contiguous()):
+        raise ValueError(f"params_out must be contiguous fp32 {(B, n_cam, 8)}")
+    need = image_augment_workspace(B, I)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or \
+            not workspace.is_contiguous() or workspace.data_ptr() % 16:
+        raise ValueError(f"workspace must be a contiguous 16-B aligned uint8 buffer of at least "
+                         f"{need} bytes")
+    _C.call("mmt_image_augment", ptr(images), B, I, H, W, ptr(rng), int(sample_offset),
+            ptr(image_camera), ptr(cam_params), n_cam, ptr(out), ptr(params_out), ptr(workspace),
+            workspace.numel(), _C.stream_ptr())
+    return out
+
+
 def _pc_weights(C: int, w1, b1, w2, b2, w_out, b_out):
     F1, F2, D = w1.shape[1], w2.shape[1], w_out.shape[1]
     for t, shape, what in ((w1, (2 * C, F1), "w1"), (b1, (F1,), "b1"), (w2, (F1, F2), "w2"),

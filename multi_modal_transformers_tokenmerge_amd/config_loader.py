@@ -28,7 +28,9 @@ which are not available on the GPU box.
   ``action_heads.continuous_loss`` ("mse" | "l1"), ``tokenizers.values.encoder`` (the
   ValueTokenizer node behind the ``Value{n}`` sets of the sequence),
   ``tokenizers.pointclouds.encoder`` (the PointCloudTokenizer node behind the ``PointCloud{n}``
-  sets, with ``num_points``), ``fp8_matmul``,
+  sets, with ``num_points``), ``tokenizers.images.augmentation`` (the image augmentation of the
+  training losses: ``cameras``, a list of CameraAugmentation's fields, and optionally
+  ``image_camera``), ``fp8_matmul``,
   ``t5_num_layers`` and ``text_tokens``.
 
 Errors follow the reference's conventions: a missing key or an unknown ``_target_`` raises
@@ -321,6 +323,21 @@ def octo_config_from_yaml(cfg: dict, name: str = "yaml"):
         keys = ("num_points", "num_neighbours_knn", "point_features", "hidden")
         kw["point_cloud_tokenizer"] = {k: (tuple(pc[k]) if k == "hidden" else pc[k])
                                        for k in keys if k in pc}
+    # image augmentation of the training losses: cameras (CameraAugmentation's fields, the ranges
+    # as pairs) and optionally image_camera
+    ia = _first(cfg, "tokenizers.images.augmentation", default=None)
+    if ia is not None:
+        if not isinstance(ia, dict) or not isinstance(ia.get("cameras"), list):
+            raise ValueError("tokenizers.images.augmentation must be a mapping with a `cameras` "
+                             f"list, got {ia!r}")
+        aug = {"cameras": [{k: (tuple(v) if isinstance(v, list) else v) for k, v in c.items()}
+                           if isinstance(c, dict) else c for c in ia["cameras"]]}
+        if ia.get("image_camera") is not None:
+            aug["image_camera"] = [int(v) for v in ia["image_camera"]]
+        extra = set(ia) - {"cameras", "image_camera"}
+        if extra:
+            raise ValueError(f"tokenizers.images.augmentation: unknown keys {sorted(extra)}")
+        kw["image_augmentation"] = aug
     t5_layers = cfg.get("t5_num_layers")
     if t5_layers:
         kw["t5"] = T5Config(num_layers=int(t5_layers))

@@ -23,8 +23,9 @@ COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-un
                 "-munsafe-fp-atomics"]
 # Files whose bit-exact contract forbids FMA contraction (ToMe canonical arithmetic;
 # pointcloud.hip and depth.hip: the point distance and the back-projection are restated in numpy
-# float32, operation by operation; their FMAs are explicit fmaf calls).
-NO_CONTRACT = {"tome.hip", "pointcloud.hip", "depth.hip"}
+# float32, operation by operation; their FMAs are explicit fmaf calls; augment.hip: the crop's
+# bilinear resample and the colour chain likewise: no FMA in the restated arithmetic).
+NO_CONTRACT = {"tome.hip", "pointcloud.hip", "depth.hip", "augment.hip"}
 # Per-file extra flags. attention.hip: no NaN semantics (every NaN there would be a bug) and the
 # IEEE mode bit off, so fmaxf on MFMA outputs is one v_max (no canonicalising v_max x, x first).
 EXTRA = {"attention.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"]}

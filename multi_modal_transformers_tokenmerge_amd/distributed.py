@@ -105,6 +105,9 @@ class DDPStep:
     # device buffers likewise: a replay after the loader rewrote them gives the other masks' step.
     # point_cloud_counts: the valid points of every cloud (Octo.generate_readouts), a static int32
     # device buffer likewise: thin clouds become absent sets on the device, inside the graph.
+    # Image augmentation (OctoConfig.image_augmentation): the step's loss augments a copy of img
+    # inside the graph, keyed by the device step counter, so every replay draws new crops; img
+    # must be uint8.
 
     def __init__(self, model, state, txt, img, act, reducer: GradAllReducer | None = None,
                  stages="auto", use_graph: bool = True, txt_next=None, values=None,
@@ -112,6 +115,8 @@ class DDPStep:
                  point_cloud_counts=None):
         self.model, self.state = model, state
         self.txt, self.img, self.act = txt, img, act
+        if getattr(model, "augmentation", None) is not None:   # ValueError now, not in a capture
+            model._check_augment(img, state.rng)
         if values is not None or model.n_values:    # ValueError now, not inside a capture
             model._check_values(values, img.shape[0])
         self.values = values

@@ -13,6 +13,19 @@ from typing import Optional
 from ...tokenizers.text.t5_base import T5Config
 
 
+def _default_image_camera(input_sequence: str) -> list:
+    """Per Image set of the sequence after the repeat expansion, as the sequencer parses it
+    (TokenSequence, the parser the model itself uses): its ordinal among the Image sets of its
+    observation block (the sets of one timestep)."""
+    from ...tokenizers.token_sequencer import Image, TokenSequence
+    out, seen = [], {}
+    for ts in TokenSequence(input_sequence).token_sequence:
+        if isinstance(ts, Image):
+            out.append(seen.get(ts.timestep, 0))
+            seen[ts.timestep] = out[-1] + 1
+    return out
+
+
 @dataclass
 class OctoConfig:
     name: str = "octo-small"
@@ -113,8 +126,51 @@ class OctoConfig:
     # num_neighbours_knn (1 .. 32, default 16), point_features (C, 3 .. 8, default 3) and hidden
     # (the two LBR widths, each 32 / 64 / 128, default (64, 64)). Required with PointCloud sets
     point_cloud_tokenizer: Optional[dict] = None
+    # image augmentation of the training losses (tokenizers/images/augment.py; YAML key
+    # tokenizers.images.augmentation): a dict with `cameras`, a list of dicts with any of scale,
+    # ratio, brightness, contrast, saturation (CameraAugmentation's fields), one per camera, and
+    # optionally `image_camera`, the camera index of every Image set of input_sequence after the
+    # repeat expansion (default: the Image sets of one observation block are cameras 0, 1, ...,
+    # repeated across blocks, so a history window shares its camera's draw). uint8 images only;
+    # applied by the compute_*_loss methods with train=True (hence the train steps and DDPStep),
+    # never by the predict_* methods. None: off, no launch added
+    image_augmentation: Optional[dict] = None
+
+    def image_camera(self) -> list:
+        """The camera index of every Image set of input_sequence after the repeat expansion:
+        image_augmentation's `image_camera` if given, else 0, 1, ... within each observation
+        block."""
+        aug = self.image_augmentation or {}
+        if aug.get("image_camera") is not None:
+            return [int(c) for c in aug["image_camera"]]
+        return _default_image_camera(self.input_sequence)
 
     def __post_init__(self):
+        if self.image_augmentation is not None:
+            from ...tokenizers.images.augment import ImageAugmentation
+            aug = self.image_augmentation
+            if not isinstance(aug, dict) or set(aug) - {"cameras", "image_camera"} or \
+                    not isinstance(aug.get("cameras"), (list, tuple)) or not aug["cameras"]:
+                raise ValueError("image_augmentation must be a dict with `cameras` (a non-empty "
+                                 f"list) and optionally `image_camera`, got {aug!r}")
+            explicit = aug.get("image_camera") is not None
+            slots = _default_image_camera(self.input_sequence)
+            if not slots:
+                raise ValueError("image_augmentation is set but input_sequence has no Image set")
+            if explicit:
+                cams = list(aug["image_camera"])
+                if len(cams) != len(slots):
+                    raise ValueError(f"image_augmentation.image_camera names {len(cams)} image "
+                                     f"sets, input_sequence has {len(slots)}")
+            elif len(aug["cameras"]) != max(slots) + 1:
+                raise ValueError(f"image_augmentation.cameras holds {len(aug['cameras'])} "
+                                 f"cameras, an observation block of input_sequence has "
+                                 f"{max(slots) + 1} Image sets (give image_camera to map them "
+                                 "otherwise)")
+            ia = ImageAugmentation(aug["cameras"], aug["image_camera"] if explicit else slots)
+            if explicit and set(ia.image_camera) != set(range(ia.n_cam)):
+                raise ValueError(f"image_augmentation.cameras holds {ia.n_cam} cameras, "
+                                 f"image_camera uses {sorted(set(ia.image_camera))}")
         if self.point_cloud_tokenizer is not None:
             import re
             from ...tokenizers.pointclouds.point_cloud_tokenizer import (
@@ -219,6 +275,12 @@ PRESETS = {
     # top-k pruning on the small geometry: 16 image tokens per block
     "octo-small-prune16": OctoConfig(name="octo-small-prune16", token_compression_sequence=TOME16,
                                      compression="prune"),
+    # configs[2] trained with Octo's primary-camera augmentation on its one camera: random resized
+    # crop (area 0.8 .. 1, aspect 0.9 .. 1.1), brightness 0.1, contrast and saturation 0.9 .. 1.1
+    "octo-small-tome16-aug": OctoConfig(
+        name="octo-small-tome16-aug", token_compression_sequence=TOME16,
+        image_augmentation=dict(cameras=[dict(scale=(0.8, 1.0), ratio=(0.9, 1.1), brightness=0.1,
+                                              contrast=(0.9, 1.1), saturation=(0.9, 1.1))])),
     # configs[2] with 8 proprioception values per observation (Value tokens, never compressed)
     "octo-small-tome16-proprio8": OctoConfig(
         name="octo-small-tome16-proprio8",

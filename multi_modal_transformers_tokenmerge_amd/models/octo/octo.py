@@ -99,6 +99,16 @@ class Octo:
             if ts.num_tokens != self.pc_tokens:
                 raise ValueError("every PointCloud set must hold the same number of tokens, got "
                                  f"{[t.num_tokens for t in pc_sets]}")
+        # image augmentation of the training losses (OctoConfig.image_augmentation): no parameter
+        self.augmentation = None
+        self.last_augmentation = None   # (augmented images, params) of the last augmented forward
+        if cfg.image_augmentation is not None:
+            from ...tokenizers.images.augment import ImageAugmentation
+            cams = cfg.image_camera()
+            if len(cams) != self.n_images:
+                raise ValueError(f"image_augmentation maps {len(cams)} image sets, the sequence "
+                                 f"has {self.n_images}")
+            self.augmentation = ImageAugmentation(cfg.image_augmentation["cameras"], cams)
         self.has_text = self.n_text > 0
         if self.has_text and cfg.text_tokens != self.n_text:
             raise ValueError("text_tokens must equal the text set sizes of input_sequence")
@@ -365,6 +375,23 @@ class Octo:
                              f"device ({self.device.type})")
         return counts.contiguous()
 
+    def _check_augment(self, images, rng):
+        """An augmented forward's inputs checked before any launch. ValueError: images not a
+        uint8 (B, n_images, H, W, 3) tensor on the model's device (fp32 frames are refused: the
+        augmentation is defined on uint8, and the stem keeps its fused uint8 route), rng
+        missing."""
+        if not torch.is_tensor(images) or images.dtype != torch.uint8:
+            raise ValueError("image_augmentation is configured: the training losses take uint8 "
+                             f"images, got {getattr(images, 'dtype', type(images))}")
+        if images.dim() != 5 or images.shape[1] != self.n_images or images.shape[-1] != 3:
+            raise ValueError(f"images {tuple(images.shape)}: expected (B, {self.n_images}, H, W, "
+                             "3) for the augmentation")
+        if images.device.type != self.device.type:
+            raise ValueError(f"images must live on the model's device ({self.device.type})")
+        if rng is None:
+            raise ValueError("image_augmentation is configured: the training losses need rng "
+                             "(the {seed, step} words the draws are keyed by)")
+
     def _check_pad_masks(self, set_pad_mask, text_pad_mask, B: int, images=None) -> bool:
         """The observation pad masks checked before any launch; returns whether one is given.
         ValueError: not a bool tensor on the model's device, set_pad_mask not (B, the set count
@@ -400,8 +427,16 @@ class Octo:
     def generate_readouts(self, text_tokens, images, train=True, rng=None, sample_offset=0,
                           positions=None, tome=None, t5_out=None, values=None, point_clouds=None,
                           fps_start=None, set_pad_mask=None, text_pad_mask=None,
-                          point_cloud_counts=None):
+                          point_cloud_counts=None, augment: bool = False):
         """Reference :91-126. Returns the final sequence (B, L_final, D) and the saved state.
+        augment: with OctoConfig.image_augmentation set, the tokenizers read an augmented copy of
+        the uint8 images (tokenizers/images/augment.py: one draw per (seed, step, sample_offset +
+        b, camera) from rng, which is then required), made before the absent cameras are zeroed;
+        `images` itself is not changed, point_clouds are not moved with the crop, and the copy
+        and its parameters stay in the saved state ("aug_images", "aug_params" (B, n_cam, 8)) and
+        on the model (last_augmentation). fp32 images are refused then. The compute_*_loss methods
+        pass their `train` flag; the predict_* methods never augment. Without
+        image_augmentation the flag does nothing.
         t5_out: the frozen T5 encoder's output for text_tokens, computed ahead (DDPStep's
         cross-step T5 pipeline); None runs the encoder here. values: the numbers behind the
         Value sets, fp32 (B, n_sets, n) or (B, n_sets * n), expected in [-1, 1]
@@ -432,7 +467,19 @@ class Octo:
         point_clouds = self._check_point_clouds(point_clouds, B, fps_start)
         padded = self._check_pad_masks(set_pad_mask, text_pad_mask, B, images)
         padded = padded or counts is not None
+        augment = bool(augment) and self.augmentation is not None
+        if augment:
+            self._check_augment(images, rng)
         st: Dict = dict(B=B, train=train, rng=rng, sample_offset=sample_offset)
+        if augment:
+            # before the pad masks: an absent camera's augmented frame is zeroed like any other
+            params = torch.empty((B, self.augmentation.n_cam, 8), dtype=torch.float32,
+                                 device=images.device)
+            with phase("fwd/augment"):
+                images = self.augmentation(images.contiguous(), rng, sample_offset,
+                                           params_out=params)
+            st["aug_images"], st["aug_params"] = images, params
+            self.last_augmentation = (images, params)
         txt, T = None, max(self.n_text, 1)
         if self.has_text:
             if t5_out is None:
@@ -544,7 +591,7 @@ class Octo:
                                         values=values, point_clouds=point_clouds,
                                         set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
                                         point_cloud_counts=point_cloud_counts,
-                                        fps_start=inject.get("fps_start"))
+                                        fps_start=inject.get("fps_start"), augment=train)
         B = xL.shape[0]
         if multi:   # the pooled readout in a tensor of its own: the split first Dense reads it
             cat = None
@@ -684,7 +731,7 @@ class Octo:
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         values=values, point_clouds=point_clouds,
                                         set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
-                                        point_cloud_counts=point_cloud_counts)
+                                        point_cloud_counts=point_cloud_counts, augment=train)
         loss, hsv = h.loss_forward(self._readout_mean(xL), actions, action_pad_mask)
         st.update(head_kind="continuous", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
@@ -727,7 +774,7 @@ class Octo:
         xL, st = self.generate_readouts(text_tokens, images, train, rng, sample_offset,
                                         values=values, point_clouds=point_clouds,
                                         set_pad_mask=set_pad_mask, text_pad_mask=text_pad_mask,
-                                        point_cloud_counts=point_cloud_counts)
+                                        point_cloud_counts=point_cloud_counts, augment=train)
         loss, hsv = h.loss_forward(self._readout_group_means(xL), actions, action_pad_mask)
         st.update(head_kind="categorical", head_sv=hsv, xL_shape=tuple(xL.shape))
         return loss, st
